@@ -485,6 +485,42 @@ int spa_overlap_refine(spa_ctx *ctx, const int32_t *labels, const uint8_t *road,
                        int64_t npix, int32_t max_labels, double threshold, uint8_t *refined,
                        void *stream);
 
+/* ---- SegNet-Basic inference (labels_from_segnet.py, models/segnet_basic.py) ---------------
+ * The network run_train_rounds.py trains on the labels and then evaluates to make the next round's labels, in test
+ * mode (BatchNorm folded into the convolutions by the caller: wt' = wt * gamma / sqrt(avg_var + 2e-5), bias = beta -
+ * avg_mean * gamma / sqrt(avg_var + 2e-5)).  Every 7x7 convolution (padding 3, stride 1) runs on the float32 matrix
+ * cores (an fmaf chain per output, float32 accumulation); no atomics: an image's outputs have the same bits whatever the
+ * batch size and its position in the batch.  Shapes outside what the kernels take are refused before anything is
+ * launched (SPA_ERR_ARG, SPA_ERR_LAYOUT): there is no library fallback.  x_layout names the storage of the input. */
+#define SPA_LAYOUT_NHWC 0     /* channels-last (B,H,W,C)                                   */
+#define SPA_LAYOUT_NCHW 1     /* planar (B,C,H,W)                                          */
+/* One encoder stage: pooled, idx = max_pooling_2d(relu(conv7x7(x; wt) + bias), 2, 2) with the argmax of every window
+ * (ky * 2 + kx, the FIRST maximum in row-major order: Chainer's own pooling kernel, segnet_basic.py:11-13), the
+ * full-resolution convolution output never stored.  Cin 3 (conv1): x (B,3,H,W) float32 0..255 planar (SPA_LAYOUT_NCHW,
+ * the cubic-resized image), standardised in the load as the dataset does ((v - mean_host[c]) / std_host[c], two float32
+ * roundings, zipped_cityscapes_road_dataset.py:87-89) and passed through Chainer's LRN (n 5, k 1, alpha 1e-4 / 5, beta
+ * 0.75, alpha not divided by n), H and W % 16 == 0; wt (49,64,4) float32 = the (64,3,7,7) weight permuted to (ky*7+kx, n,
+ * c) with c = 3 zero.  Cin 64 (conv2-4): x (B,H,W,64) channels-last (SPA_LAYOUT_NHWC), H and W even; wt (49,64,64);
+ * mean_host / std_host unused.  bias (64); pooled (B,H/2,W/2,64) float32, idx (B,H/2,W/2,64) uint8.  x and wt 16-byte
+ * aligned. */
+int spa_segnet_encode(spa_ctx *ctx, const float *x, int32_t x_layout, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                      const float *wt, const float *bias, const float *mean_host, const float *std_host, float *pooled,
+                      uint8_t *idx, void *stream);
+/* One decoder stage: y = conv7x7(upsampling_2d(x, idx)) + bias, the unpooled input (each value at its recorded
+ * position of its 2x2 block, zeros elsewhere) gathered in the load, never stored.  x, idx (B,Hh,Wh,64) float32 / uint8
+ * channels-last (what spa_segnet_encode wrote); wt (49,64,64), bias (64).  wc == bc == NULL (decode4-2): y (B,2Hh,2Wh,64)
+ * float32 channels-last.  wc (2,64), bc (2) (decode1, segnet_basic.py:80-81 + predict's F.softmax): the 1x1 classifier
+ * and the channel softmax fused, y (B,2,2Hh,2Wh) float32 planar probabilities, 2Hh and 2Wh % 16 == 0. */
+int spa_segnet_decode(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B, int32_t Hh,
+                      int32_t Wh, const float *wt, const float *bias, const float *wc, const float *bc, float *y,
+                      void *stream);
+/* SegNetBasic.predict's tail (segnet_basic.py:101-106): prob (B,2,h,w) float32 resized to (H,W) as chainercv's PIL
+ * backend does it (Image.resize(BILINEAR) per channel, mode 'F': double coefficients, a horizontal pass rounded to
+ * float32, then the vertical pass; same bits), mask (B,H,W) uint8 = argmax over the two channels (ties: 0), scores
+ * (B,2,H,W) float32 the resized probabilities or NULL.  Upscales only (H >= h, W >= w): SPA_ERR_ARG otherwise. */
+int spa_segnet_score(spa_ctx *ctx, const float *prob, int32_t B, int32_t h, int32_t w, int32_t H, int32_t W,
+                     uint8_t *mask, float *scores, void *stream);
+
 /* save_info() scoring (:398-405): per image confusion of road (B,npix) uint8 against
    gt (B,npix) int32 in {-1 ignore, 0, 1} -> out (B,4) int64 {TN, FP, FN, TP}.             */
 int spa_confusion(spa_ctx *ctx, const uint8_t *road, const int32_t *gt, int32_t B,

@@ -1,0 +1,176 @@
+#!/usr/bin/env python
+"""Labels from a trained SegNet-Basic snapshot (same CLI, outputs and save_labels() as the reference script of this
+name, which utils/run_train_rounds.py imports between training rounds), on libspalign's kernels instead of Chainer.
+See superpixel-align_amd/segnet.py for the network.
+
+Outputs per image, in --out_dir:
+  <basename>.npy          bool mask of shape eval_shape (argmax of the probabilities resized to eval_shape)
+  <basename>_scores.npy   THE MASK AGAIN: the reference's CLI path (save_each=True, labels_from_segnet.py:90-92) saves
+                          `pred` under this name too; kept byte-compatible.  save_labels(..., save_each=False) returns
+                          the float32 (2, H, W) scores instead, as run_train_rounds.py expects.
+  <basename>.png          the 3-panel figure (unless --no_figure)
+  result.json             one JSON line per image, the reference's keys in its order
+Additions: --no_figure, --batchsize (images per launch chain).  --gpu -1 (the reference's CPU mode) runs on device 0:
+there is no CPU path.  Only model 'basic' in the snapshot's args.txt is supported.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def _save_figure(d, i, pred, label, out_dir):
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    from PIL import Image
+    d._open()
+    with Image.open(d.img_zf.open(d.img_fns[i])) as f:        # the archive member (the reference opens it as a path)
+        img = np.array(f.convert('RGB'), dtype=np.uint8)
+    plt.clf()
+    fig, axes = plt.subplots(1, 3)
+    fig.set_dpi(300)
+    for a in axes:
+        a.axis('off')
+    axes[0].imshow(img)
+    axes[0].imshow(pred, alpha=0.4, cmap=plt.cm.Set1_r)
+    axes[0].set_title('Estimated road mask (input image overlayed)', fontsize=4)
+    axes[1].imshow(label == 1)
+    axes[1].set_title('Ground truth road mask', fontsize=4)
+    axes[2].imshow(pred)
+    axes[2].set_title('Estimated road mask', fontsize=4)
+    plt.savefig(os.path.join(out_dir, os.path.basename(d.img_fns[i])), bbox_inches='tight')
+    plt.close()
+
+
+def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
+                start_index, end_index, soft_label, eval_shape,
+                save_each=False, figure=True, batchsize=4):
+    """labels_from_segnet.py:24-153.  With save_each=False returns {<out_dir>/<basename>: bool mask,
+    <out_dir>/<basename>_scores: float32 (2, H, W) probabilities at eval_shape}."""
+    import torch
+    segnet = importlib.import_module('superpixel-align_amd.segnet')
+    cli = importlib.import_module('superpixel-align_amd.cli')
+    train_args = segnet.load_train_args(param_dir)
+
+    if not os.path.exists(out_dir):
+        try:
+            os.makedirs(out_dir)
+        except Exception:
+            pass
+
+    device = max(int(gpu), 0)
+    torch.cuda.set_device(device)
+    model = segnet.SegNetBasic.from_snapshot(param_dir, iteration, pred_shape=eval_shape, device=device)
+    eng = model.engine
+    in_shape = tuple(int(v) for v in train_args['input_shape'])
+    eval_shape_t = tuple(int(v) for v in eval_shape)
+
+    d = segnet.ZippedCityscapesRoadDataset(img_zip_fn, label_zip_fn, train_args['input_shape'])
+    if end_index > len(d):
+        raise ValueError(
+            'end_index option should be less than the length of dataset '
+            '{} but {} was given.'.format(len(d), end_index))
+
+    pred_and_scores = {} if not save_each else None
+    batchsize = max(int(batchsize), 1)
+    for lo in range(start_index, end_index, batchsize):
+        ids = list(range(lo, min(lo + batchsize, end_index)))
+        raws = [d.get_raw(i) for i in ids]
+        # images of one size go through one launch chain (Cityscapes: all of them)
+        groups = {}
+        for j, (img, _) in enumerate(raws):
+            groups.setdefault(img.shape, []).append(j)
+        preds, scores = [None] * len(ids), [None] * len(ids)
+        for shape, js in groups.items():
+            u8 = torch.from_numpy(np.stack([raws[j][0].transpose(1, 2, 0) for j in js])).to(eng.device)
+            x = eng.resize_cvcubic_u8(u8.contiguous(), in_shape)     # (B,3,h,w) float32 0..255, the dataset's cv2 resize
+            prob = model.forward(x)
+            mask, sc = eng.segnet_score(prob, eval_shape_t, want_scores=not save_each)
+            mask_h = mask.cpu().numpy()
+            sc_h = sc.cpu().numpy() if sc is not None else None
+            for t, j in enumerate(js):
+                preds[j] = mask_h[t]
+                scores[j] = sc_h[t] if sc_h is not None else None
+        for j, i in enumerate(ids):
+            label = raws[j][1]
+            pred = preds[j]
+            if label.shape != pred.shape:
+                raise ValueError('label %s has shape %s, the prediction %s (eval_shape)'
+                                 % (d.label_fns[i], label.shape, pred.shape))
+            conf = eng.confusion(torch.from_numpy(pred[None]).to(eng.device),
+                                 torch.from_numpy(np.ascontiguousarray(label[None])).to(eng.device)).cpu().numpy()[0]
+            sc = cli.score_from_counts(*[int(v) for v in conf])
+            pred = pred.astype(bool)
+            fn_base = os.path.splitext(os.path.basename(d.img_fns[i]))[0]
+            save_fn = os.path.join(out_dir, fn_base)
+            if save_each:
+                np.save(save_fn, pred)
+                np.save(save_fn + '_scores', pred)       # sic: the reference saves the mask under this name too
+            else:
+                pred_and_scores[save_fn] = pred
+                pred_and_scores[save_fn + '_scores'] = scores[j].astype(np.float32)
+            if figure:
+                _save_figure(d, i, pred, label, out_dir)
+            with open(os.path.join(out_dir, 'result.json'), 'a') as fp:
+                result_info = {
+                    'img_fn': d.img_fns[i],
+                    'label_fn': d.label_fns[i],
+                    'road_iou': sc['road_iou'],
+                    'non_road_iou': sc['non_road_iou'],
+                    'precision': sc['precision'],
+                    'recall': sc['recall'],
+                    'TP': sc['TP'],
+                    'FP': sc['FP'],
+                    'FN': sc['FN'],
+                }
+                result_info.update({
+                    'param_dir': param_dir,
+                    'iteration': iteration,
+                    'gpu': gpu,
+                    'img_zip_fn': img_zip_fn,
+                    'label_zip_fn': label_zip_fn,
+                    'out_dir': out_dir,
+                    'start_index': start_index,
+                    'end_index': end_index,
+                    'soft_label': soft_label,
+                    'eval_shape': eval_shape,
+                    'save_each': save_each,
+                })
+                result_info.update({'train_args': train_args})
+                print(json.dumps(result_info), file=fp)
+    del model
+    if not save_each:
+        return pred_and_scores
+
+
+def get_parser():
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--param_dir', type=str)
+    parser.add_argument('--iteration', type=int)
+    parser.add_argument('--gpu', type=int, default=-1)
+    parser.add_argument('--img_zip_fn', type=str)
+    parser.add_argument('--label_zip_fn', type=str)
+    parser.add_argument('--out_dir', type=str)
+    parser.add_argument('--start_index', type=int)
+    parser.add_argument('--end_index', type=int)
+    parser.add_argument('--soft_label', action='store_true', default=False)
+    parser.add_argument('--eval_shape', type=int, nargs=2, default=[1024, 2048])
+    parser.add_argument('--no_figure', action='store_true', default=False)
+    parser.add_argument('--batchsize', type=int, default=4)
+    return parser
+
+
+if __name__ == '__main__':
+    args = get_parser().parse_args()
+    save_labels(
+        args.param_dir, args.iteration, args.gpu, args.img_zip_fn,
+        args.label_zip_fn, args.out_dir, args.start_index, args.end_index,
+        args.soft_label, args.eval_shape, True, figure=not args.no_figure, batchsize=args.batchsize)

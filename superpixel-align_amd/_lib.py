@@ -130,6 +130,9 @@ PROTOTYPES = {
                                                  c_i32, c_p, c_p, c_p, c_p, c_p]),
     'spa_paint': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
     'spa_confusion': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i64, c_p, c_p]),
+    'spa_segnet_encode': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    'spa_segnet_decode': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
+    'spa_segnet_score': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
 }
 
 

@@ -786,6 +786,68 @@ class Engine(object):
                                   _ptr(cluster), _ptr(road), self._s()))
         return cluster, road
 
+    # ------------------------------------------------------------------ SegNet-Basic (labels_from_segnet.py)
+    LAYOUT_NHWC, LAYOUT_NCHW = 0, 1
+
+    @classmethod
+    def _layout(cls, x):
+        """Storage of a (B,C,H,W) float32 / uint8 tensor: plain contiguous -> planar, channels-last -> NHWC."""
+        if x.is_contiguous():
+            return cls.LAYOUT_NCHW
+        if x.is_contiguous(memory_format=torch.channels_last):
+            return cls.LAYOUT_NHWC
+        raise SpalignError('segnet: the input is neither contiguous nor channels-last')
+
+    def segnet_encode(self, x, wt, bias, mean=None, std=None):
+        """One encoder stage, maxpool2x2_argmax(relu(conv7x7(x) + bias)): x (B,3,H,W) float32 planar image 0..255
+        (conv1: standardised with mean / std and LRN-normalised in the load; wt (49,64,4)) or (B,64,H,W) channels-last
+        (wt (49,64,64)) -> (pooled (B,64,H/2,W/2) float32, idx (B,64,H/2,W/2) uint8), both channels-last."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+        B, C, H, W = x.shape
+        _req(wt, torch.float32, 'wt')
+        _req(bias, torch.float32, 'bias')
+        pooled = torch.empty((B, 64, H // 2, W // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        idx = torch.empty((B, 64, H // 2, W // 2), dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+        m = (ctypes.c_float * 3)(*mean) if mean is not None else None
+        s = (ctypes.c_float * 3)(*std) if std is not None else None
+        check(self._lib.spa_segnet_encode(self._ctx, _ptr(x), self._layout(x), B, H, W, C, _ptr(wt), _ptr(bias), m, s,
+                                          _ptr(pooled), _ptr(idx), self._s()))
+        return pooled, idx
+
+    def segnet_decode(self, x, idx, wt, bias, wc=None, bc=None):
+        """One decoder stage, conv7x7(unpool(x, idx)) + bias: x (B,64,h,w) float32 and idx (B,64,h,w) uint8
+        channels-last -> (B,64,2h,2w) float32 channels-last; with the classifier wc (2,64), bc (2) (decode1): softmax
+        probabilities (B,2,2h,2w) float32 planar."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and idx.dtype == torch.uint8
+        B, C, h, w = x.shape
+        assert C == 64 and tuple(idx.shape) == tuple(x.shape)
+        _req(wt, torch.float32, 'wt')
+        _req(bias, torch.float32, 'bias')
+        if wc is None:
+            y = torch.empty((B, 64, 2 * h, 2 * w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        else:
+            _req(wc, torch.float32, 'wc')
+            _req(bc, torch.float32, 'bc')
+            y = torch.empty((B, 2, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+        layout = self._layout(x)
+        if self._layout(idx) != layout:
+            raise SpalignError('segnet_decode: x and idx have different layouts')
+        check(self._lib.spa_segnet_decode(self._ctx, _ptr(x), _ptr(idx), layout, B, h, w, _ptr(wt), _ptr(bias),
+                                          _ptr(wc), _ptr(bc), _ptr(y), self._s()))
+        return y
+
+    def segnet_score(self, prob, shape, want_scores=False):
+        """prob (B,2,h,w) float32 -> (mask (B,H,W) uint8, scores (B,2,H,W) float32 or None): Pillow's BILINEAR upscale
+        of each channel to shape = (H, W), then the argmax (ties: class 0)."""
+        prob = _req(prob, torch.float32, 'prob')
+        B, C, h, w = prob.shape
+        assert C == 2
+        H, W = int(shape[0]), int(shape[1])
+        mask = torch.empty((B, H, W), dtype=torch.uint8, device=prob.device)
+        sc = torch.empty((B, 2, H, W), dtype=torch.float32, device=prob.device) if want_scores else None
+        check(self._lib.spa_segnet_score(self._ctx, _ptr(prob), B, h, w, H, W, _ptr(mask), _ptr(sc), self._s()))
+        return mask, sc
+
     def confusion(self, road, gt):
         """road (B,H,W) u8, gt (B,H,W) i32 in {-1,0,1} -> (B,4) i64 {TN, FP, FN, TP}."""
         road = _req(road, torch.uint8, 'road')
