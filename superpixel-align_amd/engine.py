@@ -26,6 +26,26 @@ def _req(t, dtype, what):
     return t
 
 
+def _out(out, shape, dtype, device):
+    """the output of a convolution wrapper: a new channels-last tensor, or the caller's (tests hand in poisoned buffers)"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device, memory_format=torch.channels_last)
+    if not (out.is_cuda and out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.is_contiguous(memory_format=torch.channels_last)):
+        raise SpalignError('out must be a channels-last CUDA tensor of dtype %s and shape %s' % (dtype, tuple(shape)))
+    return out
+
+
+def _scratch(scratch, v_shape, m_shape, device):
+    """(v, m) scratch of the Winograd wrappers: new tensors, or the caller's pair"""
+    if scratch is None:
+        return (torch.empty(v_shape, dtype=torch.float32, device=device), torch.empty(m_shape, dtype=torch.float32, device=device))
+    v, m = scratch
+    for t, shape in ((v, v_shape), (m, m_shape)):
+        if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
+            raise SpalignError('scratch must be two contiguous float32 CUDA tensors of shapes %s, %s' % (v_shape, m_shape))
+    return v, m
+
+
 class Engine(object):
     """One spa_ctx (one GPU). Not thread safe; make one per process/GPU."""
 
@@ -201,7 +221,7 @@ class Engine(object):
         l = (frag - h.float()).half()
         return torch.stack([h, l], dim=1).contiguous(), float(1.0 / t)        # (2, 2, 5, 64, 8)
 
-    def drn_layer2_f16s(self, x, wp, inv_t, bias, amax_in=None):
+    def drn_layer2_f16s(self, x, wp, inv_t, bias, amax_in=None, out=None):
         """relu(conv3x3(x; 16 -> 32 channels, stride 2, padding 1) + bias) on the 16-bit matrix cores at float32 accuracy.
         Returns y with the device word of its largest value attached as `_spa_amax`."""
         B, C, H, W = x.shape
@@ -210,7 +230,7 @@ class Engine(object):
         assert bias.dtype == torch.float32 and bias.numel() == 32 and bias.is_contiguous()
         if amax_in is None:
             amax_in = self.amax(x)
-        y = torch.empty((B, 32, (H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        y = _out(out, (B, 32, (H + 1) // 2, (W + 1) // 2), torch.float32, x.device)
         am = torch.empty(1, dtype=torch.int32, device=x.device)
         check(self._lib.spa_drn_layer2_f16s(self._ctx, _ptr(x), B, H, W, _ptr(wp), ctypes.c_float(inv_t), _ptr(bias), _ptr(amax_in),
                                             _ptr(am), _ptr(y), self._s()))
@@ -228,7 +248,7 @@ class Engine(object):
         check(self._lib.spa_drn_layer2_f32(self._ctx, _ptr(x), B, H, W, _ptr(w9), _ptr(bias), _ptr(y), self._s()))
         return y
 
-    def conv3x3_s2_f32(self, x, wt, bias, csplit, relu=True):
+    def conv3x3_s2_f32(self, x, wt, bias, csplit, relu=True, out=None, out2=None):
         """conv3x3_s2_f16s with float32 matrix instructions: wt (Cout,9,Cin) float32 (the projection's rows hold its weights at
         tap 4).  Returns (y, y2 or None)."""
         B, Cin, Hi, Wi = x.shape
@@ -237,9 +257,8 @@ class Engine(object):
         assert wt.dtype == torch.float32 and wt.is_contiguous() and tuple(wt.shape) == (Cout, 9, Cin)
         assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == Cout
         Ho, Wo = (Hi + 1) // 2, (Wi + 1) // 2
-        y = torch.empty((B, csplit, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        y2 = torch.empty((B, Cout - csplit, Ho, Wo), dtype=torch.float32, device=x.device,
-                         memory_format=torch.channels_last) if csplit < Cout else None
+        y = _out(out, (B, csplit, Ho, Wo), torch.float32, x.device)
+        y2 = _out(out2, (B, Cout - csplit, Ho, Wo), torch.float32, x.device) if csplit < Cout else None
         check(self._lib.spa_conv3x3_s2_f32(self._ctx, _ptr(x), B, Hi, Wi, Cin, _ptr(wt), Cout, int(csplit), _ptr(bias),
                                            1 if relu else 0, _ptr(y), _ptr(y2), self._s()))
         return y, y2
@@ -282,7 +301,7 @@ class Engine(object):
             parts.append(torch.stack([ph, (pf - ph.float()).half()], dim=1).reshape(-1))  # (tiles, 2, 64, 8)
         return torch.cat(parts).contiguous(), float(1.0 / t)
 
-    def conv_small_f16s(self, x, wp, inv_t, bias, cout, stride=1, n_proj=0, residual=None, relu=True, amax_in=None):
+    def conv_small_f16s(self, x, wp, inv_t, bias, cout, stride=1, n_proj=0, residual=None, relu=True, amax_in=None, out=None, out2=None):
         """relu?(conv3x3(x; Cin 16 | 32 -> cout 16 | 32, stride 1 | 2, padding 1) + bias [+ residual]) on the 16-bit matrix cores
         at float32 accuracy, optionally with the block's 1x1 stride-2 projection as a second output (n_proj = 32).
         -> (y, y2 or None); y carries the device word of its largest value as `_spa_amax`."""
@@ -292,8 +311,8 @@ class Engine(object):
         Ho, Wo = (H + stride - 1) // stride, (W + stride - 1) // stride
         if amax_in is None:
             amax_in = self.amax(x)
-        y = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        y2 = torch.empty((B, n_proj, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last) if n_proj else None
+        y = _out(out, (B, cout, Ho, Wo), torch.float32, x.device)
+        y2 = _out(out2, (B, n_proj, Ho, Wo), torch.float32, x.device) if n_proj else None
         if residual is not None:
             assert residual.dtype == torch.float32 and residual.shape == y.shape and residual.is_contiguous(memory_format=torch.channels_last)
         am = torch.empty(1, dtype=torch.int32, device=x.device)
@@ -317,7 +336,7 @@ class Engine(object):
                                      _ptr(bias), _ptr(residual), 1 if relu else 0, self._s()))
         return y
 
-    def conv3x3_f32(self, x, wt, bias, residual=None, relu=True, dilation=1):
+    def conv3x3_f32(self, x, wt, bias, residual=None, relu=True, dilation=1, out=None):
         """relu?(conv3x3(x; stride 1, padding = dilation) + bias [+ residual]) on the float32 matrix cores.
         x (B,Cin,H,W) float32 in channels-last storage, wt (Cout,9,Cin) float32, bias (Cout) float32."""
         B, Cin, H, W = x.shape
@@ -326,7 +345,7 @@ class Engine(object):
         taps = wt.shape[1]
         assert wt.dtype == torch.float32 and wt.is_contiguous() and tuple(wt.shape) == (Cout, taps, Cin) and taps in (1, 9)
         assert bias.dtype == torch.float32 and bias.is_contiguous()
-        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        y = _out(out, (B, Cout, H, W), torch.float32, x.device)
         if residual is not None:
             assert residual.dtype == torch.float32 and residual.shape == y.shape and \
                 residual.is_contiguous(memory_format=torch.channels_last)
@@ -352,7 +371,7 @@ class Engine(object):
         wt2 = torch.stack([h.view(Cout, taps, Cin // 32, 32), l.view(Cout, taps, Cin // 32, 32)], dim=3).contiguous()
         return wt2, float(1.0 / t)
 
-    def conv3x3_f16s(self, x, wt2, inv_t, bias, residual=None, relu=True, dilation=1, amax_in=None, track_amax=True):
+    def conv3x3_f16s(self, x, wt2, inv_t, bias, residual=None, relu=True, dilation=1, amax_in=None, track_amax=True, out=None):
         """conv3x3_f32 (3x3 or, with one tap, the 1x1 projection) on the 16-bit matrix cores at float32 accuracy: weights as
         two half-precision planes (split_planes), pixels split in the kernel.  Returns (y, amax of y or None)."""
         B, Cin, H, W = x.shape
@@ -360,7 +379,7 @@ class Engine(object):
         assert x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
         assert wt2.dtype == torch.float16 and wt2.is_contiguous() and tuple(wt2.shape) == (Cout, taps, Cin // 32, 2, 32) and taps in (1, 9)
         assert bias.dtype == torch.float32 and bias.is_contiguous()
-        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        y = _out(out, (B, Cout, H, W), torch.float32, x.device)
         if residual is not None:
             assert residual.dtype == torch.float32 and residual.shape == y.shape and \
                 residual.is_contiguous(memory_format=torch.channels_last)
@@ -379,7 +398,7 @@ class Engine(object):
                                              _ptr(y), self._s()))
         return y, amax_out
 
-    def conv3x3_s2_f16s(self, x, wt2, inv_t, bias, csplit, relu=True, amax_in=None):
+    def conv3x3_s2_f16s(self, x, wt2, inv_t, bias, csplit, relu=True, amax_in=None, out=None, out2=None):
         """3x3 stride-2 padding-1 convolution (+ the block's 1x1 stride-2 projection as output channels csplit..) on the
         16-bit matrix cores at float32 accuracy: one pass over x.  wt2 = split_planes of the (Cout,9,Cin) weights (the
         projection's rows hold its weights at tap 4).  Returns (y, y2 or None, amax of y)."""
@@ -389,9 +408,8 @@ class Engine(object):
         assert wt2.dtype == torch.float16 and wt2.is_contiguous() and tuple(wt2.shape) == (Cout, 9, Cin // 32, 2, 32)
         assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == Cout
         Ho, Wo = (Hi + 1) // 2, (Wi + 1) // 2
-        y = torch.empty((B, csplit, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        y2 = torch.empty((B, Cout - csplit, Ho, Wo), dtype=torch.float32, device=x.device,
-                         memory_format=torch.channels_last) if csplit < Cout else None
+        y = _out(out, (B, csplit, Ho, Wo), torch.float32, x.device)
+        y2 = _out(out2, (B, Cout - csplit, Ho, Wo), torch.float32, x.device) if csplit < Cout else None
         if amax_in is None:
             amax_in = self.amax(x)
         amax_out = torch.empty(1, dtype=torch.int32, device=x.device)
@@ -412,7 +430,7 @@ class Engine(object):
         u = torch.einsum('ij,kcjl,ml->imkc', G, weight.detach().double(), G)
         return u.reshape(G.shape[0] ** 2, weight.shape[0], weight.shape[1]).float().contiguous()
 
-    def conv3x3_wino_f32(self, x, u, bias, residual=None, relu=True, dilation=1):
+    def conv3x3_wino_f32(self, x, u, bias, residual=None, relu=True, dilation=1, out=None, scratch=None):
         """relu?(conv3x3(x; stride 1, padding = dilation) + bias [+ residual]) by Winograd F(2x2,3x3) (u of 16
         positions) or F(4x4,3x3) (36 positions) on the float32 matrix cores.  x (B,Cin,H,W) float32 channels-last,
         u = winograd_weights(weight, tile), bias (Cout) float32."""
@@ -422,15 +440,14 @@ class Engine(object):
         assert x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
         assert u.dtype == torch.float32 and u.is_contiguous() and tuple(u.shape) == (npos, Cout, Cin)
         assert bias.dtype == torch.float32 and bias.is_contiguous()
-        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        y = _out(out, (B, Cout, H, W), torch.float32, x.device)
         if residual is not None:
             assert residual.dtype == torch.float32 and residual.shape == y.shape and \
                 residual.is_contiguous(memory_format=torch.channels_last)
         tiles, fn = (self._lib.spa_wino_tiles, self._lib.spa_conv3x3_wino_f32) if npos == 16 else \
             (self._lib.spa_wino4_tiles, self._lib.spa_conv3x3_wino4_f32)
         T = int(tiles(B, H, W, int(dilation)))
-        v = torch.empty((npos, T, Cin), dtype=torch.float32, device=x.device)       # per call: stream safe
-        m = torch.empty((npos, T, Cout), dtype=torch.float32, device=x.device)
+        v, m = _scratch(scratch, (npos, T, Cin), (npos, T, Cout), x.device)       # per call: stream safe
         check(fn(self._ctx, _ptr(x), B, H, W, Cin, _ptr(u), Cout, _ptr(bias), _ptr(residual),
                  1 if relu else 0, int(dilation), _ptr(v), _ptr(m), _ptr(y), self._s()))
         return y
@@ -460,7 +477,8 @@ class Engine(object):
         check(self._lib.spa_amax_f32(self._ctx, _ptr(x), x.numel(), _ptr(a), self._s()))
         return a
 
-    def conv3x3_wino_f16s(self, x, u2, cs, bias, residual=None, relu=True, dilation=1, amax_in=None, track_amax=True, _keep=None):
+    def conv3x3_wino_f16s(self, x, u2, cs, bias, residual=None, relu=True, dilation=1, amax_in=None, track_amax=True, _keep=None,
+                          out=None, scratch=None):
         """conv3x3_wino_f32's F(4x4,3x3) with the GEMMs on the 16-bit matrix cores at float32 accuracy (two half-precision
         planes per operand, three products).  (u2, cs) = winograd_weights_split(weight).  Returns (y, amax of y or None);
         amax_in: the amax the producing call returned for x (computed here when None)."""
@@ -469,7 +487,7 @@ class Engine(object):
         assert x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
         assert u2.dtype == torch.float16 and u2.is_contiguous() and tuple(u2.shape) == (36, Cout, Cin // 32, 2, 32)
         assert bias.dtype == torch.float32 and bias.is_contiguous() and cs.dtype == np.float32 and cs.shape == (36,)
-        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        y = _out(out, (B, Cout, H, W), torch.float32, x.device)
         if residual is not None:
             assert residual.dtype == torch.float32 and residual.shape == y.shape and \
                 residual.is_contiguous(memory_format=torch.channels_last)
@@ -477,8 +495,7 @@ class Engine(object):
             amax_in = self.amax(x)
         amax_out = torch.empty(1, dtype=torch.int32, device=x.device) if track_amax else None
         T = int(self._lib.spa_wino4_tiles(B, H, W, int(dilation)))
-        v = torch.empty((36, T, Cin), dtype=torch.float32, device=x.device)       # two float16 planes = 4 bytes per element
-        m = torch.empty((36, T, Cout), dtype=torch.float32, device=x.device)
+        v, m = _scratch(scratch, (36, T, Cin), (36, T, Cout), x.device)       # v: two float16 planes = 4 bytes per element
         if _keep is not None:                    # tools / tests: look at the transformed operands
             _keep['v'], _keep['m'] = v, m
         check(self._lib.spa_conv3x3_wino4_f16s(self._ctx, _ptr(x), B, H, W, Cin, _ptr(u2), cs.ctypes.data, Cout, _ptr(bias),
@@ -502,7 +519,7 @@ class Engine(object):
                                          _ptr(residual), 1 if relu else 0, int(dilation), _ptr(y), self._s()))
         return y
 
-    def conv_bf16_light(self, x, wt, bias, residual=None, relu=True, stride=1, dilation=1):
+    def conv_bf16_light(self, x, wt, bias, residual=None, relu=True, stride=1, dilation=1, out=None):
         """The light layers of the bf16 DRN (models/drn.py:134-151, 195-203) on libspalign's kernel: x (B,Cin,H,W) bf16
         channels-last, wt (Cout,taps,Cin) bf16 with taps 9 (3x3, padding = dilation) or 1 (1x1), stride 1 or 2."""
         B, Cin, H, W = x.shape
@@ -511,7 +528,7 @@ class Engine(object):
         assert wt.dtype == torch.bfloat16 and wt.is_contiguous() and tuple(wt.shape) == (Cout, taps, Cin) and taps in (1, 9)
         assert bias.dtype == torch.float32 and bias.is_contiguous()
         Ho, Wo = (H + stride - 1) // stride, (W + stride - 1) // stride
-        y = torch.empty((B, Cout, Ho, Wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+        y = _out(out, (B, Cout, Ho, Wo), torch.bfloat16, x.device)
         if residual is not None:
             assert residual.dtype == torch.bfloat16 and residual.shape == y.shape and \
                 residual.is_contiguous(memory_format=torch.channels_last)
