@@ -521,6 +521,33 @@ int spa_segnet_decode(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t 
 int spa_segnet_score(spa_ctx *ctx, const float *prob, int32_t B, int32_t h, int32_t w, int32_t H, int32_t W,
                      uint8_t *mask, float *scores, void *stream);
 
+/* ---- SegNet-Basic training (train_segnet.py --model basic) ----------------------------------------------------
+ * The 7x7 convolutions (padding 3, stride 1, no bias) of the training step on the float32 matrix cores; BatchNorm,
+ * ReLU, pooling and the loss are the caller's.  (H, W) is the convolution's resolution: multiples of 16 for conv1
+ * (the network input), even for the 64-channel layers (1/2 .. 1/8 of it).  wt is the
+ * packed (49,64,Cp) = (ky*7+kx, n, c) weight of spa_segnet_encode (Cp 4 for conv1, channel 3 zero).  Input forms (x,
+ * idx): Cin 3: the planar (B,3,H,W) float32 image (SPA_LAYOUT_NCHW), standardised with mean_host / std_host and
+ * LRN-normalised in the load as spa_segnet_encode does, idx NULL; Cin 64, idx NULL: a (B,H,W,64) channels-last map;
+ * Cin 64 with idx: the decoder input, x and idx (B,H/2,W/2,64) channels-last, unpooled through idx in the load.  No
+ * atomics: every call gives the same bits on every run and device.  Workspaces belong to the context. */
+/* y (B,H,W,64) float32 channels-last = conv7x7(x; wt).  stats != NULL: stats[0..63] = sum of y, stats[64..127] = sum
+ * of y^2 over (B,H,W) per channel, float64 (per-workgroup float32 partials, summed in a fixed order). */
+int spa_segnet_train_forward(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B, int32_t H,
+                             int32_t W, int32_t Cin, const float *wt, const float *mean_host, const float *std_host,
+                             float *y, double *stats, void *stream);
+/* The input gradient of a 64-channel layer.  dy (B,H,W,64) channels-last, wt (49,64,64) the layer's forward weight.
+ * idx NULL (conv2-4): dx (B,H,W,64) = the gradient at the layer's input.  idx (B,H/2,W/2,64) (decoder layers, the
+ * index map the layer unpooled with): dx (B,H/2,W/2,64) = the gradient at the pooled input, the full-resolution
+ * gradient at the position idx selects in each 2x2 block. */
+int spa_segnet_train_dgrad(spa_ctx *ctx, const float *dy, const float *wt, const uint8_t *idx, int32_t B, int32_t H,
+                           int32_t W, float *dx, void *stream);
+/* dw (49,64,Cp) float32 = sum over (b,y,x) of dy[b,y,x,n] * in[b, y + ky - 3, x + kx - 3, c], in the input form (x,
+ * idx, Cin) of the layer's forward.  Split-K over a fixed number of pixel chunks that depends on (B, H, W) only,
+ * the chunks' float32 sums added in chunk order in float64 and rounded once. */
+int spa_segnet_train_wgrad(spa_ctx *ctx, const float *dy, const float *x, const uint8_t *idx, int32_t x_layout,
+                           int32_t B, int32_t H, int32_t W, int32_t Cin, const float *mean_host, const float *std_host,
+                           float *dw, void *stream);
+
 /* save_info() scoring (:398-405): per image confusion of road (B,npix) uint8 against
    gt (B,npix) int32 in {-1 ignore, 0, 1} -> out (B,4) int64 {TN, FP, FN, TP}.             */
 int spa_confusion(spa_ctx *ctx, const uint8_t *road, const int32_t *gt, int32_t B,

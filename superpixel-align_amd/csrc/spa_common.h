@@ -85,6 +85,9 @@ enum {
     WS_RNG_JOFF,     // offsets of the superpixels' swap lists
     WS_RUNS,         // connectivity: per-row lists of run starts (B,H,W) i32, used from the front of each row
     WS_DEBUG,        // diagnostic builds: in-kernel stamps (tools read it with spa_debug_peek)
+    WS_SEGNET_BNPART,  // SegNet training forward: per-workgroup per-channel partial sums of y and y^2
+    WS_SEGNET_WROT,    // SegNet training dgrad: the weights rotated 180 degrees, in/out channels swapped
+    WS_SEGNET_WGRAD,   // SegNet training wgrad: the split-K partial weight gradients (chunk, 49, 64, Cp)
     WS_COUNT
 };
 

@@ -865,6 +865,74 @@ class Engine(object):
         check(self._lib.spa_segnet_score(self._ctx, _ptr(prob), B, h, w, H, W, _ptr(mask), _ptr(sc), self._s()))
         return mask, sc
 
+    # ---- SegNet-Basic training (segnet_train.py).  Maps are (B,H,W,64) contiguous tensors (channels-last storage);
+    # conv1's input is the planar (B,3,H,W) float32 image 0..255.
+    def _train_input(self, x, idx):
+        """-> (layout, Cin, H, W at the convolution's resolution) of a training input form (see spalign.h)."""
+        if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
+            raise SpalignError('segnet_train: x must be a contiguous (B,3,H,W) or (B,H,W,64) float32 CUDA tensor')
+        if idx is not None:
+            _req(idx, torch.uint8, 'idx')
+            if x.shape[3] != 64 or tuple(idx.shape) != tuple(x.shape):
+                raise SpalignError('segnet_train: the decoder input and its index map must both be (B,h,w,64)')
+            return self.LAYOUT_NHWC, 64, 2 * x.shape[1], 2 * x.shape[2]
+        if x.shape[1] == 3:
+            return self.LAYOUT_NCHW, 3, x.shape[2], x.shape[3]
+        if x.shape[3] != 64:
+            raise SpalignError('segnet_train: x must be (B,3,H,W) or (B,H,W,64), got %s' % (tuple(x.shape),))
+        return self.LAYOUT_NHWC, 64, x.shape[1], x.shape[2]
+
+    def segnet_train_forward(self, x, wt, idx=None, mean=None, std=None, stats=True, out=None):
+        """y = conv7x7(x; wt), no bias, at full resolution: x the planar image (conv1, wt (49,64,4), standardised with
+        mean / std and LRN-normalised in the load), a (B,H,W,64) map, or a decoder's (B,H/2,W/2,64) input with its
+        index map idx.  -> (y (B,H,W,64) float32, (sum y, sum y^2) (2,64) float64 or None)."""
+        layout, cin, H, W = self._train_input(x, idx)
+        _req(wt, torch.float32, 'wt')
+        B = x.shape[0]
+        y = out if out is not None else torch.empty((B, H, W, 64), dtype=torch.float32, device=x.device)
+        _req(y, torch.float32, 'out')
+        st = torch.empty((2, 64), dtype=torch.float64, device=x.device) if stats else None
+        m = (ctypes.c_float * 3)(*mean) if mean is not None else None
+        s = (ctypes.c_float * 3)(*std) if std is not None else None
+        check(self._lib.spa_segnet_train_forward(self._ctx, _ptr(x), _ptr(idx), layout, B, H, W, cin, _ptr(wt), m, s,
+                                                 _ptr(y), _ptr(st), self._s()))
+        return y, st
+
+    def segnet_train_dgrad(self, dy, wt, idx=None, out=None):
+        """The input gradient of a 64-channel layer: dy (B,H,W,64), wt (49,64,64) the forward weight.  idx None ->
+        (B,H,W,64); idx (B,H/2,W/2,64) (decoder layers) -> the gradient at the pooled input (B,H/2,W/2,64)."""
+        dy = _req(dy, torch.float32, 'dy')
+        _req(wt, torch.float32, 'wt')
+        B, H, W, C = dy.shape
+        if idx is not None:
+            _req(idx, torch.uint8, 'idx')
+            shape = (B, H // 2, W // 2, 64)
+            if tuple(idx.shape) != shape:
+                raise SpalignError('segnet_train_dgrad: idx must be %s, got %s' % (shape, tuple(idx.shape)))
+        else:
+            shape = (B, H, W, 64)
+        dx = out if out is not None else torch.empty(shape, dtype=torch.float32, device=dy.device)
+        _req(dx, torch.float32, 'out')
+        check(self._lib.spa_segnet_train_dgrad(self._ctx, _ptr(dy), _ptr(wt), _ptr(idx), B, H, W, _ptr(dx), self._s()))
+        return dx
+
+    def segnet_train_wgrad(self, dy, x, idx=None, mean=None, std=None, out=None):
+        """dw (49,64,Cp) = the weight gradient of conv7x7 for the output gradient dy (B,H,W,64) and the layer's input
+        form (x, idx) as segnet_train_forward takes it (Cp 4 for conv1, channel 3 zero)."""
+        dy = _req(dy, torch.float32, 'dy')
+        layout, cin, H, W = self._train_input(x, idx)
+        B = x.shape[0]
+        if tuple(dy.shape) != (B, H, W, 64):
+            raise SpalignError('segnet_train_wgrad: dy must be %s, got %s' % ((B, H, W, 64), tuple(dy.shape)))
+        dw = out if out is not None else torch.empty((49, 64, 4 if cin == 3 else 64), dtype=torch.float32,
+                                                     device=dy.device)
+        _req(dw, torch.float32, 'out')
+        m = (ctypes.c_float * 3)(*mean) if mean is not None else None
+        s = (ctypes.c_float * 3)(*std) if std is not None else None
+        check(self._lib.spa_segnet_train_wgrad(self._ctx, _ptr(dy), _ptr(x), _ptr(idx), layout, B, H, W, cin, m, s,
+                                               _ptr(dw), self._s()))
+        return dw
+
     def confusion(self, road, gt):
         """road (B,H,W) u8, gt (B,H,W) i32 in {-1,0,1} -> (B,4) i64 {TN, FP, FN, TP}."""
         road = _req(road, torch.uint8, 'road')

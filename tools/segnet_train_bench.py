@@ -1,0 +1,108 @@
+#!/usr/bin/env python
+"""SegNet-Basic training on the MI355X: the time of one training step (segnet_train.SegNetTrainer.step, MomentumSGD)
+and its images/s at B images of 512 x 1024, and for every layer the device-event time of each kernel pass (forward,
+dgrad, wgrad) with its TFLOP/s from the layer shape (segnet.layer_flops: forward and dgrad each cost the layer's
+forward FLOPs, wgrad too) against the 157.3 TF float32 matrix peak.  Random weights and inputs: the time does not
+depend on the values.
+
+  python tools/segnet_train_bench.py [--batch 4] [--iters 10] [--out profiles/segnet_train_bench_b4.json]
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+segnet = importlib.import_module('superpixel-align_amd.segnet')
+st = importlib.import_module('superpixel-align_amd.segnet_train')
+engine = importlib.import_module('superpixel-align_amd.engine')
+PEAK_TF = 157.3
+
+
+def event_ms(fn, iters):
+    fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=4)
+    ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--height', type=int, default=512)
+    ap.add_argument('--width', type=int, default=1024)
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    B, H, W = a.batch, a.height, a.width
+    torch.cuda.set_device(0)
+    eng = engine.Engine(0)
+    flops = segnet.layer_flops(H, W)
+    g = torch.Generator(device='cuda').manual_seed(0)
+    rows = {}
+    for i, name in enumerate(segnet.LAYERS):
+        if i < 4:
+            h_, w_ = H >> i, W >> i
+            x = (torch.rand((B, 3, H, W), generator=g, device='cuda') * 255 if i == 0 else
+                 torch.randn((B, h_, w_, 64), generator=g, device='cuda'))
+            idx = None
+        else:
+            s = 7 - i
+            h_, w_ = H >> s, W >> s
+            x = torch.randn((B, h_ // 2, w_ // 2, 64), generator=g, device='cuda')
+            idx = torch.randint(0, 4, (B, h_ // 2, w_ // 2, 64), generator=g, device='cuda', dtype=torch.uint8)
+        cp = 4 if i == 0 else 64
+        wt = torch.randn((49, 64, cp), generator=g, device='cuda') * 0.01
+        dy = torch.randn((B, h_, w_, 64), generator=g, device='cuda')
+        f = flops[name] * B
+        row = {'shape': [B, h_, w_]}
+        row['fwd_ms'] = event_ms(lambda: eng.segnet_train_forward(x, wt, idx, segnet.MEAN, segnet.STD), a.iters)
+        if i > 0:
+            row['dgrad_ms'] = event_ms(lambda: eng.segnet_train_dgrad(dy, wt, idx), a.iters)
+        row['wgrad_ms'] = event_ms(lambda: eng.segnet_train_wgrad(dy, x, idx, segnet.MEAN, segnet.STD), a.iters)
+        for k in ('fwd', 'dgrad', 'wgrad'):
+            if k + '_ms' in row:
+                tf = f / (row[k + '_ms'] * 1e-3) / 1e12
+                row[k + '_tflops'] = tf
+                row[k + '_share_of_peak'] = tf / PEAK_TF
+        rows[name] = row
+        del x, dy, idx
+    torch.cuda.empty_cache()
+    # the whole step
+    tr = st.SegNetTrainer(st.init_params(0), st.MomentumSGD(0.01, weight_decay=0.0005), st.softmax_cross_entropy,
+                          engine=eng)
+    img = torch.rand((B, 3, H, W), generator=g, device='cuda') * 255
+    t = torch.randint(0, 2, (B, H, W), generator=g, device='cuda')
+    tr.step(img, t)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.iters):
+        tr.step(img, t)
+    torch.cuda.synchronize()
+    step_ms = (time.perf_counter() - t0) * 1e3 / a.iters
+    kern_ms = sum(r.get(k, 0.0) for r in rows.values() for k in ('fwd_ms', 'dgrad_ms', 'wgrad_ms'))
+    total_f = sum(flops.values()) * B * 3 - flops['conv1'] * B
+    out = {'batch': B, 'input': [H, W], 'step_ms': step_ms, 'images_per_s': B * 1000.0 / step_ms,
+           'conv_kernels_ms': kern_ms, 'conv_tflop_per_step': total_f / 1e12,
+           'conv_tflops': total_f / (kern_ms * 1e-3) / 1e12, 'step_tflops': total_f / (step_ms * 1e-3) / 1e12,
+           'peak_tflops_f32_matrix': PEAK_TF, 'layers': rows, 'device': torch.cuda.get_device_name(0)}
+    s = json.dumps(out, indent=2)
+    print(s)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as fp:
+            fp.write(s + '\n')
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,224 @@
+#!/usr/bin/env python
+"""Train SegNet-Basic on estimated road labels (same CLI, defaults and outputs as the reference script of this name,
+which utils/run_train_rounds.py runs between labelling rounds), on libspalign's kernels instead of Chainer.  See
+superpixel-align_amd/segnet_train.py for the network, the optimizers and the dataset.
+
+Outputs in the result directory (create_result_dir(prefix), or --result_dir):
+  args.txt               the arguments, JSON (sort_keys, indent 4)
+  log                    LogReport's JSON list, one entry per --log_interval: iteration, epoch, main/loss (mean over
+                         the interval), lr, elapsed_time and, where validation ran, val/main/iou/road,
+                         val/main/iou/non_road, val/main/miou, val_/main/precision, val_/main/recall, val_/main/FP, FN
+  snapshot_iter_<N>      every --val_interval: the npz labels_from_segnet.py reads (updater/model:main/predictor/...)
+                         plus the optimizer, iteration, lr and iterator state that --resume reads
+Only --model basic, one process, and units of 'iteration' (an 'epoch' interval is converted with the dataset size).
+"""
+import argparse
+import importlib
+import json
+import os
+import random
+import re
+import shutil
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def get_parser():
+    parser = argparse.ArgumentParser()
+    parser.add_argument(
+        '--train_img_zip', type=str, default='data/cityscapes_train_imgs.0.zip',
+        help='If it\'s given, ZippedEstimatedCityscapesDataset will be used.')
+    parser.add_argument(
+        '--train_label_zip', type=str, default='results/estimated_train_labels.0.zip',
+        help='If it\'s given, ZippedEstimatedCityscapesDataset will be used.')
+    parser.add_argument(
+        '--val_img_zip', type=str, default='data/cityscapes_val_imgs.0.zip',
+        help='If it\'s given, ZippedCityscapesRoadDataset will be used.')
+    parser.add_argument(
+        '--val_label_zip', type=str, default='data/cityscapes_gtFine_val_labels.0.zip',
+        help='If it\'s given, ZippedCityscapesRoadDataset will be used.')
+    parser.add_argument('--model', type=str, default='basic', choices=['normal', 'basic'])
+    parser.add_argument('--batchsize', type=int, default=4)
+    parser.add_argument('--lr', type=float, default=0.01)
+    parser.add_argument('--decay_iteration', type=int, default=300)
+    parser.add_argument('--weight_decay', type=float, default=0.0005)
+    parser.add_argument('--train_limit', type=str, nargs=2, default=['1000', 'iteration'])
+    parser.add_argument('--optimizer', type=str, default='MomentumSGD', choices=['Adam', 'MomentumSGD'])
+    parser.add_argument('--input_shape', type=int, nargs=2, default=[512, 1024])
+    parser.add_argument('--random', action='store_true', default=False)
+    parser.add_argument('--communicator', type=str, default='single_node')
+    parser.add_argument('--prefix', type=str, default='results/round_1')
+    parser.add_argument('--resume', type=str, default=None)
+    parser.add_argument('--log_interval', type=str, nargs=2, default=['50', 'iteration'])
+    parser.add_argument('--val_interval', type=str, nargs=2, default=['50', 'iteration'])
+    parser.add_argument('--eval_shape', type=int, nargs=2, default=[1024, 2048])
+    parser.add_argument('--result_dir', type=str, default=None)
+    parser.add_argument(
+        '--use_soft_label', action='store_true', default=False,
+        help='If True, softmax cross entorpy with soft labels is used as loss function')
+    parser.add_argument(
+        '--use_mse', action='store_true', default=False,
+        help='If True, mean squared error is used as loss function')
+    parser.add_argument('--n_use_data', type=int, default=None)
+    return parser
+
+
+def get_args(argv=None):
+    return get_parser().parse_args(argv)
+
+
+def create_result_dir(prefix):
+    """<prefix>_<time>_<i> for the first i >= 0 that does not exist yet; copies this script into it."""
+    stamp = time.strftime('%Y-%m-%d_%H-%M-%S')
+    i = 0
+    result_dir = '{}_{}_{}'.format(prefix, stamp, i)
+    while os.path.exists(result_dir):
+        i += 1
+        result_dir = re.sub('_[0-9]+$', '_{}'.format(i), result_dir)
+    os.makedirs(result_dir)
+    shutil.copy(os.path.abspath(__file__), os.path.join(result_dir, os.path.basename(__file__)))
+    return result_dir
+
+
+def check_supported(args):
+    """The refusals: the VGG-style 'normal' SegNet (segnet.load_train_args' message) and multi-rank launches."""
+    if args.model != 'basic':
+        raise ValueError("--model '%s' is not supported: only SegNet-Basic ('basic') is implemented%s"
+                         % (args.model, " (the VGG-style 'normal' SegNet is not)" if args.model == 'normal' else ''))
+    ws = int(os.environ.get('WORLD_SIZE', os.environ.get('OMPI_COMM_WORLD_SIZE', '1')))
+    if ws > 1:
+        raise RuntimeError('train_segnet.py runs in one process only (WORLD_SIZE=%d): the multi-node BatchNorm of a '
+                           'multi-rank run (cross-rank batch statistics) is not implemented' % ws)
+
+
+def _iterations(interval, n_data, batchsize):
+    n, unit = int(interval[0]), interval[1]
+    if unit == 'iteration':
+        return n
+    if unit == 'epoch':
+        return max(1, int(np.ceil(n * n_data / float(batchsize))))
+    raise ValueError('unknown interval unit %r' % unit)
+
+
+def evaluate(trainer, valid, eval_shape, batchsize):
+    """SemanticSegmentationEvaluator + PrecisionRecallEvaluator over the validation set with the inference network
+    (BN folded from the running statistics), predicting as labels_from_segnet.py does -> the report entries."""
+    import torch
+    model = trainer.predictor(eval_shape)
+    eng = trainer.eng
+    in_shape = tuple(int(v) for v in valid.resize_shape)
+    conf = np.zeros(4, np.int64)                                    # TN, FP, FN, TP
+    for lo in range(0, len(valid), batchsize):
+        raws = [valid.get_raw(i) for i in range(lo, min(lo + batchsize, len(valid)))]
+        for img, label in raws:
+            u8 = torch.from_numpy(np.ascontiguousarray(img.transpose(1, 2, 0))[None]).to(eng.device)
+            x = eng.resize_cvcubic_u8(u8.contiguous(), in_shape)
+            mask, _ = eng.segnet_score(model.forward(x), tuple(eval_shape))
+            gt = torch.from_numpy(np.ascontiguousarray(label[None])).to(eng.device)
+            conf += eng.confusion(mask, gt).cpu().numpy()[0]
+    TN, FP, FN, TP = [int(v) for v in conf]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        iou_road = TP / float(TP + FP + FN) if TP + FP + FN else float('nan')
+        iou_non = TN / float(TN + FN + FP) if TN + FN + FP else float('nan')
+        prec = TP / float(TP + FP) if TP + FP else float('nan')
+        rec = TP / float(TP + FN) if TP + FN else float('nan')
+    return {'val/main/iou/road': iou_road, 'val/main/iou/non_road': iou_non,
+            'val/main/miou': float(np.nanmean([iou_road, iou_non])),
+            'val/main/class_accuracy/road': rec,
+            'val_/main/precision': prec, 'val_/main/recall': rec, 'val_/main/FP': FP, 'val_/main/FN': FN}
+
+
+def main(argv=None):
+    import torch
+    args = get_args(argv)
+    check_supported(args)
+    st = importlib.import_module('superpixel-align_amd.segnet_train')
+    segnet = importlib.import_module('superpixel-align_amd.segnet')
+
+    random.seed(0)
+    np.random.seed(0)
+    torch.manual_seed(0)
+    print(json.dumps(vars(args), indent=4, sort_keys=True))
+
+    soft_label = args.use_soft_label or args.use_mse
+    train = st.ZippedEstimatedCityscapesDataset(args.train_img_zip, args.train_label_zip, args.input_shape,
+                                                args.random, soft_label)
+    n_train = len(train) if args.n_use_data is None else min(args.n_use_data, len(train))
+    print('train dataset:', n_train)
+    valid = segnet.ZippedCityscapesRoadDataset(args.val_img_zip, args.val_label_zip, args.input_shape)
+    print('valid dataset:', len(valid))
+
+    lossfun = st.loss_function(args.use_soft_label, args.use_mse)
+    if args.optimizer == 'Adam':
+        opt = st.Adam()
+    else:
+        opt = st.MomentumSGD(args.lr, weight_decay=args.weight_decay)
+    torch.cuda.set_device(0)
+    trainer = st.SegNetTrainer(st.init_params(0), opt, lossfun, device=0)
+    it = st.ShuffledIterator(n_train, args.batchsize)
+
+    result_dir = args.result_dir if args.result_dir is not None else create_result_dir(args.prefix)
+    os.makedirs(result_dir, exist_ok=True)
+    with open(os.path.join(result_dir, 'args.txt'), 'w') as fp:
+        json.dump(vars(args), fp, indent=4, sort_keys=True)
+
+    iteration = 0
+    log = []
+    if args.resume is not None:
+        params, state, t, lr, iteration, it_state, rnd = st.load_snapshot_state(args.resume)
+        trainer = st.SegNetTrainer(params, opt, lossfun, engine=trainer.eng)
+        opt.t = t
+        if args.optimizer == 'MomentumSGD':
+            opt.lr = lr
+        opt.state = {k: {n: torch.as_tensor(v).to(trainer.eng.device) for n, v in s.items()} for k, s in state.items()}
+        it.load(it_state)
+        np.random.set_state(rnd)
+        log_fn = os.path.join(os.path.dirname(os.path.abspath(args.resume)), 'log')
+        if os.path.exists(log_fn):
+            log = [e for e in json.load(open(log_fn)) if e['iteration'] <= iteration]
+
+    stop = _iterations(args.train_limit, n_train, args.batchsize)
+    log_every = _iterations(args.log_interval, n_train, args.batchsize)
+    val_every = _iterations(args.val_interval, n_train, args.batchsize)
+    decay = args.decay_iteration if args.optimizer == 'MomentumSGD' else 0
+    dev = trainer.eng.device
+    losses = []
+    t0 = time.time()
+    while iteration < stop:
+        ids = it.next_indices()
+        batch = [train.get_example(i) for i in ids]
+        img = torch.from_numpy(np.stack([b[0] for b in batch])).to(dev)
+        lab = torch.from_numpy(np.stack([b[1] for b in batch])).to(dev)
+        losses.append(trainer.step(img, lab))
+        lr_used = opt.lr                                             # observe_lr: Adam's is alpha_t of this step
+        iteration += 1
+        if decay > 0 and iteration % decay == 0:
+            opt.lr *= 0.1                                            # ExponentialShift('lr', 0.1)
+        report = {}
+        if iteration % val_every == 0:
+            report.update(evaluate(trainer, valid, args.eval_shape, args.batchsize))
+        if iteration % log_every == 0:
+            entry = {'epoch': it.epoch, 'iteration': iteration, 'main/loss': float(np.mean(losses)),
+                     'lr': lr_used, 'elapsed_time': time.time() - t0}
+            entry.update(report)
+            log.append(entry)
+            losses = []
+            with open(os.path.join(result_dir, 'log'), 'w') as fp:
+                json.dump(log, fp, indent=4)
+            print(json.dumps({k: entry.get(k) for k in ('iteration', 'main/loss', 'val/main/iou/road',
+                                                        'val_/main/precision', 'val_/main/recall', 'lr',
+                                                        'elapsed_time')}))
+        if iteration % val_every == 0:
+            st.save_snapshot(os.path.join(result_dir, 'snapshot_iter_{}'.format(iteration)), trainer, iteration,
+                             opt.lr, it.state())
+    return result_dir
+
+
+if __name__ == '__main__':
+    main()
