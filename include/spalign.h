@@ -547,6 +547,19 @@ int spa_segnet_train_dgrad(spa_ctx *ctx, const float *dy, const float *wt, const
 int spa_segnet_train_wgrad(spa_ctx *ctx, const float *dy, const float *x, const uint8_t *idx, int32_t x_layout,
                            int32_t B, int32_t H, int32_t W, int32_t Cin, const float *mean_host, const float *std_host,
                            float *dw, void *stream);
+/* The same three passes on the bf16 matrix cores (train_segnet.py --dtype bf16), with the same arguments, shapes,
+ * layouts and refusals.  Operands and outputs stay float32 in memory; every product operand is the round-to-nearest-even
+ * bf16 of the float32 value the float32 pass multiplies (the standardised, LRN-normalised conv1 input, the map or
+ * unpooled value, dy, the weight), and the products accumulate in float32 (v_mfma_f32_16x16x32_bf16).  y, dx, the BN
+ * sums and dw are formed as above: float32 per workgroup or chunk, float64 across them in a fixed order, no atomics. */
+int spa_segnet_train_forward_bf16(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B,
+                                  int32_t H, int32_t W, int32_t Cin, const float *wt, const float *mean_host,
+                                  const float *std_host, float *y, double *stats, void *stream);
+int spa_segnet_train_dgrad_bf16(spa_ctx *ctx, const float *dy, const float *wt, const uint8_t *idx, int32_t B,
+                                int32_t H, int32_t W, float *dx, void *stream);
+int spa_segnet_train_wgrad_bf16(spa_ctx *ctx, const float *dy, const float *x, const uint8_t *idx, int32_t x_layout,
+                                int32_t B, int32_t H, int32_t W, int32_t Cin, const float *mean_host,
+                                const float *std_host, float *dw, void *stream);
 
 /* save_info() scoring (:398-405): per image confusion of road (B,npix) uint8 against
    gt (B,npix) int32 in {-1 ignore, 0, 1} -> out (B,4) int64 {TN, FP, FN, TP}.             */

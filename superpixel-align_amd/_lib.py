@@ -138,6 +138,11 @@ PROTOTYPES = {
     'spa_segnet_train_dgrad': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
     'spa_segnet_train_wgrad': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p,
                                               c_p]),
+    'spa_segnet_train_forward_bf16': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p,
+                                                     c_p, c_p, c_p]),
+    'spa_segnet_train_dgrad_bf16': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
+    'spa_segnet_train_wgrad_bf16': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p,
+                                                   c_p, c_p]),
 }
 
 

@@ -886,6 +886,14 @@ class Engine(object):
         """y = conv7x7(x; wt), no bias, at full resolution: x the planar image (conv1, wt (49,64,4), standardised with
         mean / std and LRN-normalised in the load), a (B,H,W,64) map, or a decoder's (B,H/2,W/2,64) input with its
         index map idx.  -> (y (B,H,W,64) float32, (sum y, sum y^2) (2,64) float64 or None)."""
+        return self._segnet_train_forward(self._lib.spa_segnet_train_forward, x, wt, idx, mean, std, stats, out)
+
+    def segnet_train_forward_bf16(self, x, wt, idx=None, mean=None, std=None, stats=True, out=None):
+        """segnet_train_forward on the bf16 matrix cores: the same float32 arguments and outputs, every product
+        operand rounded to bf16 (round to nearest even), float32 accumulation."""
+        return self._segnet_train_forward(self._lib.spa_segnet_train_forward_bf16, x, wt, idx, mean, std, stats, out)
+
+    def _segnet_train_forward(self, fn, x, wt, idx, mean, std, stats, out):
         layout, cin, H, W = self._train_input(x, idx)
         _req(wt, torch.float32, 'wt')
         B = x.shape[0]
@@ -894,13 +902,19 @@ class Engine(object):
         st = torch.empty((2, 64), dtype=torch.float64, device=x.device) if stats else None
         m = (ctypes.c_float * 3)(*mean) if mean is not None else None
         s = (ctypes.c_float * 3)(*std) if std is not None else None
-        check(self._lib.spa_segnet_train_forward(self._ctx, _ptr(x), _ptr(idx), layout, B, H, W, cin, _ptr(wt), m, s,
-                                                 _ptr(y), _ptr(st), self._s()))
+        check(fn(self._ctx, _ptr(x), _ptr(idx), layout, B, H, W, cin, _ptr(wt), m, s, _ptr(y), _ptr(st), self._s()))
         return y, st
 
     def segnet_train_dgrad(self, dy, wt, idx=None, out=None):
         """The input gradient of a 64-channel layer: dy (B,H,W,64), wt (49,64,64) the forward weight.  idx None ->
         (B,H,W,64); idx (B,H/2,W/2,64) (decoder layers) -> the gradient at the pooled input (B,H/2,W/2,64)."""
+        return self._segnet_train_dgrad(self._lib.spa_segnet_train_dgrad, dy, wt, idx, out)
+
+    def segnet_train_dgrad_bf16(self, dy, wt, idx=None, out=None):
+        """segnet_train_dgrad with dy and the weight rounded to bf16, float32 accumulation."""
+        return self._segnet_train_dgrad(self._lib.spa_segnet_train_dgrad_bf16, dy, wt, idx, out)
+
+    def _segnet_train_dgrad(self, fn, dy, wt, idx, out):
         dy = _req(dy, torch.float32, 'dy')
         _req(wt, torch.float32, 'wt')
         B, H, W, C = dy.shape
@@ -913,12 +927,19 @@ class Engine(object):
             shape = (B, H, W, 64)
         dx = out if out is not None else torch.empty(shape, dtype=torch.float32, device=dy.device)
         _req(dx, torch.float32, 'out')
-        check(self._lib.spa_segnet_train_dgrad(self._ctx, _ptr(dy), _ptr(wt), _ptr(idx), B, H, W, _ptr(dx), self._s()))
+        check(fn(self._ctx, _ptr(dy), _ptr(wt), _ptr(idx), B, H, W, _ptr(dx), self._s()))
         return dx
 
     def segnet_train_wgrad(self, dy, x, idx=None, mean=None, std=None, out=None):
         """dw (49,64,Cp) = the weight gradient of conv7x7 for the output gradient dy (B,H,W,64) and the layer's input
         form (x, idx) as segnet_train_forward takes it (Cp 4 for conv1, channel 3 zero)."""
+        return self._segnet_train_wgrad(self._lib.spa_segnet_train_wgrad, dy, x, idx, mean, std, out)
+
+    def segnet_train_wgrad_bf16(self, dy, x, idx=None, mean=None, std=None, out=None):
+        """segnet_train_wgrad with dy and the input form rounded to bf16, float32 accumulation."""
+        return self._segnet_train_wgrad(self._lib.spa_segnet_train_wgrad_bf16, dy, x, idx, mean, std, out)
+
+    def _segnet_train_wgrad(self, fn, dy, x, idx, mean, std, out):
         dy = _req(dy, torch.float32, 'dy')
         layout, cin, H, W = self._train_input(x, idx)
         B = x.shape[0]
@@ -929,8 +950,7 @@ class Engine(object):
         _req(dw, torch.float32, 'out')
         m = (ctypes.c_float * 3)(*mean) if mean is not None else None
         s = (ctypes.c_float * 3)(*std) if std is not None else None
-        check(self._lib.spa_segnet_train_wgrad(self._ctx, _ptr(dy), _ptr(x), _ptr(idx), layout, B, H, W, cin, m, s,
-                                               _ptr(dw), self._s()))
+        check(fn(self._ctx, _ptr(dy), _ptr(x), _ptr(idx), layout, B, H, W, cin, m, s, _ptr(dw), self._s()))
         return dw
 
     def confusion(self, road, gt):

@@ -13,6 +13,12 @@ updates the running averages with decay 0.9 and the unbiased variance.  BatchNor
 the index maps, the classifier and the loss are torch ops; every 7x7 convolution and its two gradients is a kernel.
 The optimizers are Chainer's MomentumSGD (v = 0.9 v - lr g; p += v) with WeightDecay and ExponentialShift, and
 Chainer's Adam.  `reference_loss` restates the whole step in float64 torch ops (F.conv2d), for the tests.
+
+dtype 'bf16' (SegNetTrainer(..., dtype='bf16'), train_segnet.py --dtype bf16) runs the 7x7 passes on the bf16 matrix
+cores (csrc/spa_segnet_train_bf16.hip): every product operand (conv input, weight, output gradient) is rounded to bf16,
+the products accumulate in float32, and everything else -- the float32 master weights, BatchNorm, pooling, the
+classifier, the loss and the optimizers -- is the float32 path unchanged.  `reference_loss(..., bf16_operands=True)`
+restates that step in float64.
 """
 import os
 import zipfile
@@ -23,6 +29,8 @@ from . import segnet
 from .segnet import BN_EPS, DECODERS, ENCODERS, LAYERS, MEAN, STD
 
 BN_DECAY = 0.9
+DTYPES = ('fp32', 'bf16')
+DTYPE_KEY = 'extensions/dtype'        # the snapshot entry that records the dtype of the run that wrote it
 BETA_INIT = 0.001
 PARAM_KEYS = tuple([n + '/W' for n in LAYERS] + ['%s_bn/%s' % (n, p) for n in LAYERS for p in ('gamma', 'beta')]
                    + ['conv_classifier/W', 'conv_classifier/b'])
@@ -120,17 +128,62 @@ def bn_update(avg_mean, avg_var, mean, var_biased, m):
 
 
 # ------------------------------------------------------------------------------- float64 restatement
-def reference_loss(P, S, img, t, lossfun, idx_maps=None, acts=None):
+def bf16_round(t):
+    """The operand rounding of the bf16 passes: t rounded to bfloat16 (round to nearest even, subnormals kept),
+    returned in t's dtype.  It is torch's own conversion, so float64 values are rounded through float32, as the
+    kernels round the float32 values of the float32 path."""
+    return t.to(_torch().bfloat16).to(t.dtype)
+
+
+def _rounding_functions():
+    torch = _torch()
+
+    class RoundOperand(torch.autograd.Function):
+        """forward: bf16_round; backward: the gradient passes unchanged (it reaches the float32 master weights)"""
+
+        @staticmethod
+        def forward(ctx, x):
+            return bf16_round(x)
+
+        @staticmethod
+        def backward(ctx, g):
+            return g
+
+    class RoundGradient(torch.autograd.Function):
+        """forward: identity; backward: the output gradient rounded, as the dgrad and wgrad passes round dy"""
+
+        @staticmethod
+        def forward(ctx, y):
+            return y.view_as(y)
+
+        @staticmethod
+        def backward(ctx, g):
+            return bf16_round(g)
+
+    return RoundOperand, RoundGradient
+
+
+def conv7_bf16_ref(x, w):
+    """F.conv2d(x, w, padding=3) with the bf16 passes' operands: x and w rounded by bf16_round, and in the backward
+    the output gradient too; the products and sums in x's dtype."""
+    F = _torch().nn.functional
+    RoundOperand, RoundGradient = _rounding_functions()
+    return RoundGradient.apply(F.conv2d(RoundOperand.apply(x), RoundOperand.apply(w), padding=3))
+
+
+def reference_loss(P, S, img, t, lossfun, idx_maps=None, acts=None, bf16_operands=False):
     """The training forward in float64 torch ops on (B,C,H,W) tensors: P the parameters (requires_grad float64),
     S the running statistics (updated in place), img (B,3,H,W) 0..255.  idx_maps (the four pooling index maps
     (B,H,W,64) uint8, e.g. the kernels') replace the argmax, so near-ties cannot send the two sides down different
-    branches.  acts (a list) receives the pooled activations relu(bn(y)) (B,H,W,64).  -> (loss, [idx maps used])."""
+    branches.  acts (a list) receives the pooled activations relu(bn(y)) (B,H,W,64).  bf16_operands: every 7x7
+    convolution is conv7_bf16_ref (the bf16 step's operand rounding).  -> (loss, [idx maps used])."""
     torch = _torch()
     F = torch.nn.functional
+    conv7 = conv7_bf16_ref if bf16_operands else (lambda x, w: F.conv2d(x, w, padding=3))
     h = conv1_input(img)
     pools = []
     for i, name in enumerate(ENCODERS):
-        y = F.conv2d(h, P[name + '/W'], padding=3)
+        y = conv7(h, P[name + '/W'])
         h = _bn_ref(P, S, name, y)
         a = F.relu(h).permute(0, 2, 3, 1)
         if acts is not None:
@@ -145,7 +198,7 @@ def reference_loss(P, S, img, t, lossfun, idx_maps=None, acts=None):
         pools.append(idx)
         h = p.permute(0, 3, 1, 2)
     for name, idx in zip(DECODERS, pools[::-1]):
-        y = F.conv2d(unpool_ref(h, idx.permute(0, 3, 1, 2).long()), P[name + '/W'], padding=3)
+        y = conv7(unpool_ref(h, idx.permute(0, 3, 1, 2).long()), P[name + '/W'])
         h = _bn_ref(P, S, name, y)
     score = F.conv2d(h, P['conv_classifier/W'], P['conv_classifier/b'])
     return lossfun(score, t), pools
@@ -235,13 +288,16 @@ def _functions():
     torch = _torch()
 
     class Conv7(torch.autograd.Function):
-        """y = conv7x7(x; wp) on the kernels; backward: dgrad (not for conv1) and split-K wgrad"""
+        """y = conv7x7(x; wp) on the kernels; backward: dgrad (not for conv1) and split-K wgrad.  bf16: the passes
+        on the bf16 matrix cores (same arguments, float32 in and out)."""
 
         @staticmethod
-        def forward(ctx, x, wp, idx, eng):
-            y, stats = eng.segnet_train_forward(x, wp, idx, MEAN, STD)
+        def forward(ctx, x, wp, idx, eng, bf16=False):
+            fwd = eng.segnet_train_forward_bf16 if bf16 else eng.segnet_train_forward
+            y, stats = fwd(x, wp, idx, MEAN, STD)
             ctx.save_for_backward(x, wp, idx)
             ctx.eng = eng
+            ctx.bf16 = bf16
             ctx.mark_non_differentiable(stats)
             return y, stats
 
@@ -249,12 +305,14 @@ def _functions():
         def backward(ctx, gy, _gstats):
             x, wp, idx = ctx.saved_tensors
             eng = ctx.eng
+            dgrad = eng.segnet_train_dgrad_bf16 if ctx.bf16 else eng.segnet_train_dgrad
+            wgrad = eng.segnet_train_wgrad_bf16 if ctx.bf16 else eng.segnet_train_wgrad
             gy = gy.contiguous()
             dx = None
             if ctx.needs_input_grad[0]:
-                dx = eng.segnet_train_dgrad(gy, wp, idx)
-            dw = eng.segnet_train_wgrad(gy, x, idx, MEAN, STD) if ctx.needs_input_grad[1] else None
-            return dx, dw, None, None
+                dx = dgrad(gy, wp, idx)
+            dw = wgrad(gy, x, idx, MEAN, STD) if ctx.needs_input_grad[1] else None
+            return dx, dw, None, None, None
 
     class BatchNorm(torch.autograd.Function):
         """BN with given batch statistics over (B,H,W) of a (B,H,W,64) map; the standard backward through them"""
@@ -282,9 +340,12 @@ _FN = []
 
 class SegNetTrainer(object):
     """Parameters, running statistics and the optimizer of one SegNetBasic on one GPU.  P: float32 tensors keyed as
-    the snapshot (conv1/W, conv1_bn/gamma, ..., conv_classifier/b), S: the running statistics."""
+    the snapshot (conv1/W, conv1_bn/gamma, ..., conv_classifier/b), S: the running statistics.  dtype 'fp32' or
+    'bf16': the operands of the 7x7 passes (see the module docstring); P, S and the optimizer are float32 in both."""
 
-    def __init__(self, params, optimizer, lossfun, engine=None, device=None):
+    def __init__(self, params, optimizer, lossfun, engine=None, device=None, dtype='fp32'):
+        if dtype not in DTYPES:
+            raise ValueError('SegNetTrainer: dtype must be one of %s, got %r' % (DTYPES, dtype))
         torch = _torch()
         from .engine import Engine
         if not _FN:
@@ -296,6 +357,7 @@ class SegNetTrainer(object):
         self.N = {n: int(np.asarray(params.get(n + '_bn/N', 0))) for n in LAYERS}
         self.opt = optimizer
         self.lossfun = lossfun
+        self.dtype = dtype
 
     def loss(self, img, t, trace=None):
         """img (B,3,H,W) float32 0..255 on the device (after augmentation, before standardisation), t the labels ->
@@ -320,7 +382,7 @@ class SegNetTrainer(object):
             return BatchNorm.apply(y, P[name + '_bn/gamma'], P[name + '_bn/beta'], mean.float(), rstd)
 
         for name in ENCODERS:
-            y, stats = Conv7.apply(h, pack_w(P[name + '/W']), None, self.eng)
+            y, stats = Conv7.apply(h, pack_w(P[name + '/W']), None, self.eng, self.dtype == 'bf16')
             a = torch.relu(bn(name, y, stats))
             h, idx = pool_argmax_nhwc(a)
             h = h.contiguous()
@@ -328,7 +390,7 @@ class SegNetTrainer(object):
         if trace is not None:
             trace.extend(pools)
         for name, idx in zip(DECODERS, pools[::-1]):
-            y, stats = Conv7.apply(h, pack_w(P[name + '/W']), idx, self.eng)
+            y, stats = Conv7.apply(h, pack_w(P[name + '/W']), idx, self.eng, self.dtype == 'bf16')
             h = bn(name, y, stats)
         score = torch.matmul(h, P['conv_classifier/W'].view(2, 64).t()) + P['conv_classifier/b']
         return self.lossfun(score.permute(0, 3, 1, 2), t)
@@ -365,8 +427,8 @@ OPT = 'updater/optimizer:main/'
 
 def save_snapshot(path, trainer, iteration, lr, iterator_state, extra=None):
     """A Chainer-style npz: updater/model:main/predictor/<link>/<param> (what segnet.load_snapshot reads), the
-    optimizer state under updater/optimizer:main/predictor/<link>/<param>/<state>, the iteration, lr, the iterator
-    and numpy's random state (so --resume continues bit for bit)."""
+    optimizer state under updater/optimizer:main/predictor/<link>/<param>/<state>, the iteration, lr, the iterator,
+    numpy's random state (so --resume continues bit for bit) and, under DTYPE_KEY, the trainer's dtype."""
     d = {}
     for k, v in trainer.params_numpy().items():
         d[segnet.PREFIX + k] = v
@@ -384,11 +446,19 @@ def save_snapshot(path, trainer, iteration, lr, iterator_state, extra=None):
     d['extensions/np_random/pos'] = np.asarray(st[2])
     d['extensions/np_random/has_gauss'] = np.asarray(st[3])
     d['extensions/np_random/cached_gaussian'] = np.asarray(st[4])
+    d[DTYPE_KEY] = np.asarray(getattr(trainer, 'dtype', 'fp32'))
     for k, v in (extra or {}).items():
         d[k] = np.asarray(v)
     tmp = path + '.tmp.npz'
     np.savez(tmp, **d)
     os.replace(tmp, path)
+
+
+def snapshot_dtype(path):
+    """The dtype a snapshot was trained with: 'fp32' or 'bf16' ('fp32' for a snapshot that does not record one).
+    Either kind resumes in either dtype: the master weights and the optimizer state are float32 in both."""
+    with np.load(path) as z:
+        return str(z[DTYPE_KEY]) if DTYPE_KEY in z.files else 'fp32'
 
 
 def load_snapshot_state(path):

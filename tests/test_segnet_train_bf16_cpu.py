@@ -1,0 +1,164 @@
+"""CPU tests of the bf16 SegNet-Basic training mode: the library exports the bf16 entry points, train_segnet.py's
+reference flag set is unchanged and --dtype is read in front of it, the float64 restatement's operand rounding is
+round-to-nearest-even bf16 (ties and subnormals included), and snapshots record the dtype they were trained with."""
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip('torch')
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+segnet = importlib.import_module('superpixel-align_amd.segnet')
+st = importlib.import_module('superpixel-align_amd.segnet_train')
+train_segnet = importlib.import_module('train_segnet')
+
+BF16_SYMBOLS = ('spa_segnet_train_forward_bf16', 'spa_segnet_train_dgrad_bf16', 'spa_segnet_train_wgrad_bf16')
+
+
+def test_library_exports_bf16_entry_points(spa):
+    L = spa._lib.lib()
+    for name in BF16_SYMBOLS:
+        assert hasattr(L, name), name
+        assert name in spa._lib.PROTOTYPES
+    engine = importlib.import_module('superpixel-align_amd.engine')
+    for m in ('segnet_train_forward_bf16', 'segnet_train_dgrad_bf16', 'segnet_train_wgrad_bf16'):
+        assert callable(getattr(engine.Engine, m))
+
+
+def test_reference_flags_unchanged():
+    a = vars(train_segnet.get_args([]))
+    assert 'dtype' not in a
+    assert a == vars(train_segnet.get_parser().parse_args([]))
+    with pytest.raises(SystemExit):                       # the reference parser does not take it
+        train_segnet.get_args(['--dtype', 'bf16'])
+
+
+def test_dtype_pre_parser():
+    assert train_segnet.get_dtype_args([]) == ('fp32', [])
+    assert train_segnet.get_dtype_args(['--batchsize', '2', '--dtype', 'bf16']) == ('bf16', ['--batchsize', '2'])
+    assert train_segnet.get_dtype_args(['--dtype=fp32', '--lr', '0.1']) == ('fp32', ['--lr', '0.1'])
+    for bad in ('fp16', 'float32', 'BF16'):
+        with pytest.raises(SystemExit):
+            train_segnet.get_dtype_args(['--dtype', bad])
+        with pytest.raises(SystemExit):                   # main() refuses before it reads any data
+            train_segnet.main(['--dtype', bad])
+
+
+def _rne_bf16_bits(f32):
+    """round-to-nearest-even of float32 values to bf16, on the bit patterns (NaN excluded)"""
+    u = f32.view(np.uint32).astype(np.uint64)
+    lsb = (u >> 16) & 1
+    return ((u + 0x7fff + lsb) >> 16).astype(np.uint16)
+
+
+def test_rounding_hook_is_rne_bf16():
+    one = 0x3f800000
+    bits = np.array([
+        one, one + 0x7fff, one + 0x8000, one + 0x8001, one + 0x18000,   # below, at (even: down), above a tie; odd tie: up
+        0x3f808000, 0x3f818000,                                         # ties between 1 + 2^-7 k, both parities
+        0x00000001, 0x00008000, 0x00018000, 0x0000ffff, 0x007fffff,     # subnormals: ties, the largest
+        0x00800000, 0x7f7fffff, 0x7f7f7fff,                             # smallest normal; the largest finite values
+        0x80000001, 0x80008000, 0xbf808000, 0x80000000, 0x00000000,     # negative values, -0, +0
+        0x7f800000, 0xff800000], np.uint32)                             # +-inf
+    rng = np.random.RandomState(0)
+    bits = np.concatenate([bits, rng.randint(0, 2 ** 31 - 1, 20000).astype(np.uint32) * np.uint32(2)])
+    bits = bits[~np.isnan(bits.view(np.float32))]
+    f = bits.view(np.float32)
+    got = st.bf16_round(torch.from_numpy(f.copy()))
+    assert got.dtype == torch.float32
+    want = (_rne_bf16_bits(f).astype(np.uint32) << 16).view(np.float32)
+    assert np.array_equal(got.numpy().view(np.uint32), want.view(np.uint32))
+    assert torch.equal(got, torch.from_numpy(f.copy()).to(torch.bfloat16).float())
+    # float64 values are rounded through float32, as torch converts them; the result stays float64
+    d = torch.from_numpy(f.astype(np.float64))
+    g64 = st.bf16_round(d)
+    assert g64.dtype == torch.float64 and torch.equal(g64, got.double())
+    # NaN stays NaN
+    assert torch.isnan(st.bf16_round(torch.tensor([float('nan')]))).all()
+
+
+def test_rounding_hook_in_reference_step():
+    """bf16_operands rounds the conv operands (and, in the backward, the output gradients); off by default"""
+    p = st.init_params(3)
+    img = torch.rand((1, 3, 16, 32), dtype=torch.float64, generator=torch.Generator().manual_seed(1)) * 255
+    t = torch.randint(-1, 2, (1, 16, 32), generator=torch.Generator().manual_seed(2))
+
+    def run(**kw):
+        P = {k: torch.tensor(p[k], dtype=torch.float64, requires_grad=True) for k in st.PARAM_KEYS}
+        S = {k: torch.tensor(p[k], dtype=torch.float64) for k in st.STAT_KEYS}
+        loss, maps = st.reference_loss(P, S, img, t, st.softmax_cross_entropy, **kw)
+        return loss, maps, torch.autograd.grad(loss, [P['conv2/W']])[0]
+
+    l0, maps, g0 = run()
+    ld, _, gd = run(idx_maps=maps, bf16_operands=False)
+    lr, _, gr = run(idx_maps=maps, bf16_operands=True)
+    assert ld.item() == l0.item() and torch.equal(gd, g0)
+    assert lr.item() != l0.item() and abs(lr.item() - l0.item()) < 1e-2 * abs(l0.item())
+    assert float((gr - g0).norm() / g0.norm()) < 0.2          # measured 0.051 (a 1 x 16 x 32 batch)
+    # the rounded convolution: operands rounded forward, the gradient passes to the unrounded operand
+    x = torch.randn((1, 2, 5, 6), dtype=torch.float64, requires_grad=True)
+    w = torch.randn((3, 2, 7, 7), dtype=torch.float64, requires_grad=True)
+    y = st.conv7_bf16_ref(x, w)
+    F = torch.nn.functional
+    assert torch.equal(y, F.conv2d(st.bf16_round(x), st.bf16_round(w), padding=3))
+    g = torch.randn_like(y)
+    gx, gw = torch.autograd.grad(y, [x, w], g)
+    xr, wr = st.bf16_round(x).detach().requires_grad_(True), st.bf16_round(w).detach().requires_grad_(True)
+    hx, hw = torch.autograd.grad(F.conv2d(xr, wr, padding=3), [xr, wr], st.bf16_round(g))
+    assert torch.equal(gx, hx) and torch.equal(gw, hw)
+
+
+class _FakeTrainer(object):
+    """what save_snapshot reads from a trainer, without a GPU"""
+
+    def __init__(self, dtype=None):
+        self._p = st.init_params(1)
+        self.opt = st.MomentumSGD(0.01)
+        self.opt.t = 3
+        self.opt.state = {'conv1/W': {'v': torch.ones((64, 3, 7, 7))}}
+        if dtype is not None:
+            self.dtype = dtype
+
+    def params_numpy(self):
+        out = dict(self._p)
+        for n in segnet.LAYERS:
+            out[n + '_bn/N'] = np.asarray(2)
+        return out
+
+
+@pytest.mark.parametrize('dtype', ['fp32', 'bf16'])
+def test_snapshot_round_trips_dtype(tmp_path, dtype):
+    d = tmp_path / 'run'
+    d.mkdir()
+    json.dump({'model': 'basic', 'input_shape': [32, 64], 'dtype': dtype}, open(str(d / 'args.txt'), 'w'))
+    it = st.ShuffledIterator(5, 2)
+    path = str(d / 'snapshot_iter_10')
+    st.save_snapshot(path, _FakeTrainer(dtype), 10, 0.01, it.state())
+    assert st.snapshot_dtype(path) == dtype
+    params, state, t, lr, iteration, its, rnd = st.load_snapshot_state(path)
+    assert (t, lr, iteration) == (3, 0.01, 10)
+    # labels_from_segnet.py's reader takes it unchanged
+    args, snap, params2 = segnet.load_snapshot(str(d), 10)
+    for k in st.PARAM_KEYS:
+        assert np.array_equal(params2[k], params[k]), k
+
+
+def test_snapshot_without_dtype_is_fp32(tmp_path):
+    path = str(tmp_path / 'snapshot_iter_1')
+    st.save_snapshot(path, _FakeTrainer(), 1, 0.01, st.ShuffledIterator(3, 1).state())
+    assert st.snapshot_dtype(path) == 'fp32'
+    with np.load(path) as z:
+        np.savez(str(tmp_path / 'old.npz'), **{k: z[k] for k in z.files if k != st.DTYPE_KEY})
+    assert st.snapshot_dtype(str(tmp_path / 'old.npz')) == 'fp32'
+
+
+def test_trainer_refuses_unknown_dtype():
+    with pytest.raises(ValueError, match='dtype'):
+        st.SegNetTrainer(st.init_params(0), st.MomentumSGD(), st.softmax_cross_entropy, engine=object(),
+                         dtype='fp16')

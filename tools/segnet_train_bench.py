@@ -2,10 +2,10 @@
 """SegNet-Basic training on the MI355X: the time of one training step (segnet_train.SegNetTrainer.step, MomentumSGD)
 and its images/s at B images of 512 x 1024, and for every layer the device-event time of each kernel pass (forward,
 dgrad, wgrad) with its TFLOP/s from the layer shape (segnet.layer_flops: forward and dgrad each cost the layer's
-forward FLOPs, wgrad too) against the 157.3 TF float32 matrix peak.  Random weights and inputs: the time does not
-depend on the values.
+forward FLOPs, wgrad too) against the matrix peak of the dtype: 157.3 TF float32, 16 x that (2516.8 TF dense) bf16.
+Random weights and inputs: the time does not depend on the values.
 
-  python tools/segnet_train_bench.py [--batch 4] [--iters 10] [--out profiles/segnet_train_bench_b4.json]
+  python tools/segnet_train_bench.py [--dtype fp32|bf16] [--batch 4] [--iters 10] [--out profiles/segnet_train_bench_b4.json]
 """
 import argparse
 import importlib
@@ -22,7 +22,7 @@ sys.path.insert(0, ROOT)
 segnet = importlib.import_module('superpixel-align_amd.segnet')
 st = importlib.import_module('superpixel-align_amd.segnet_train')
 engine = importlib.import_module('superpixel-align_amd.engine')
-PEAK_TF = 157.3
+PEAK_TF = {'fp32': 157.3, 'bf16': 16 * 157.3}
 
 
 def event_ms(fn, iters):
@@ -42,11 +42,15 @@ def main():
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--height', type=int, default=512)
     ap.add_argument('--width', type=int, default=1024)
+    ap.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'])
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     B, H, W = a.batch, a.height, a.width
+    sfx = '_bf16' if a.dtype == 'bf16' else ''
+    peak = PEAK_TF[a.dtype]
     torch.cuda.set_device(0)
     eng = engine.Engine(0)
+    fwd, dgrad, wgrad = (getattr(eng, 'segnet_train_' + k + sfx) for k in ('forward', 'dgrad', 'wgrad'))
     flops = segnet.layer_flops(H, W)
     g = torch.Generator(device='cuda').manual_seed(0)
     rows = {}
@@ -66,21 +70,21 @@ def main():
         dy = torch.randn((B, h_, w_, 64), generator=g, device='cuda')
         f = flops[name] * B
         row = {'shape': [B, h_, w_]}
-        row['fwd_ms'] = event_ms(lambda: eng.segnet_train_forward(x, wt, idx, segnet.MEAN, segnet.STD), a.iters)
+        row['fwd_ms'] = event_ms(lambda: fwd(x, wt, idx, segnet.MEAN, segnet.STD), a.iters)
         if i > 0:
-            row['dgrad_ms'] = event_ms(lambda: eng.segnet_train_dgrad(dy, wt, idx), a.iters)
-        row['wgrad_ms'] = event_ms(lambda: eng.segnet_train_wgrad(dy, x, idx, segnet.MEAN, segnet.STD), a.iters)
+            row['dgrad_ms'] = event_ms(lambda: dgrad(dy, wt, idx), a.iters)
+        row['wgrad_ms'] = event_ms(lambda: wgrad(dy, x, idx, segnet.MEAN, segnet.STD), a.iters)
         for k in ('fwd', 'dgrad', 'wgrad'):
             if k + '_ms' in row:
                 tf = f / (row[k + '_ms'] * 1e-3) / 1e12
                 row[k + '_tflops'] = tf
-                row[k + '_share_of_peak'] = tf / PEAK_TF
+                row[k + '_share_of_peak'] = tf / peak
         rows[name] = row
         del x, dy, idx
     torch.cuda.empty_cache()
     # the whole step
     tr = st.SegNetTrainer(st.init_params(0), st.MomentumSGD(0.01, weight_decay=0.0005), st.softmax_cross_entropy,
-                          engine=eng)
+                          engine=eng, dtype=a.dtype)
     img = torch.rand((B, 3, H, W), generator=g, device='cuda') * 255
     t = torch.randint(0, 2, (B, H, W), generator=g, device='cuda')
     tr.step(img, t)
@@ -94,8 +98,13 @@ def main():
     total_f = sum(flops.values()) * B * 3 - flops['conv1'] * B
     out = {'batch': B, 'input': [H, W], 'step_ms': step_ms, 'images_per_s': B * 1000.0 / step_ms,
            'conv_kernels_ms': kern_ms, 'conv_tflop_per_step': total_f / 1e12,
-           'conv_tflops': total_f / (kern_ms * 1e-3) / 1e12, 'step_tflops': total_f / (step_ms * 1e-3) / 1e12,
-           'peak_tflops_f32_matrix': PEAK_TF, 'layers': rows, 'device': torch.cuda.get_device_name(0)}
+           'conv_tflops': total_f / (kern_ms * 1e-3) / 1e12, 'step_tflops': total_f / (step_ms * 1e-3) / 1e12}
+    if a.dtype == 'fp32':
+        out['peak_tflops_f32_matrix'] = peak
+    else:
+        out.update({'dtype': 'bf16', 'peak_tflops_bf16_matrix': peak, 'conv_share_of_peak': out['conv_tflops'] / peak,
+                    'step_outside_conv_kernels_ms': step_ms - kern_ms})
+    out.update({'layers': rows, 'device': torch.cuda.get_device_name(0)})
     s = json.dumps(out, indent=2)
     print(s)
     if a.out:

@@ -11,6 +11,13 @@ Outputs in the result directory (create_result_dir(prefix), or --result_dir):
   snapshot_iter_<N>      every --val_interval: the npz labels_from_segnet.py reads (updater/model:main/predictor/...)
                          plus the optimizer, iteration, lr and iterator state that --resume reads
 Only --model basic, one process, and units of 'iteration' (an 'epoch' interval is converted with the dataset size).
+
+--dtype {fp32,bf16} (this implementation's addition, parsed in front of the reference flags; default fp32): bf16 runs
+every 7x7 convolution pass of a training step on the bf16 matrix cores, with float32 accumulation, float32 master
+weights, BatchNorm and optimizer.  The dtype goes into args.txt and every snapshot.  --resume continues bit for bit in
+the snapshot's own dtype, and a float32 snapshot may also be resumed in bf16 or the other way round (the weights and the
+optimizer state are float32 in both).  Validation always runs the float32 inference network, and labels_from_segnet.py
+reads the snapshots of either dtype.
 """
 import argparse
 import importlib
@@ -71,6 +78,17 @@ def get_parser():
 
 def get_args(argv=None):
     return get_parser().parse_args(argv)
+
+
+def get_dtype_args(argv=None):
+    """-> (--dtype, the remaining arguments for get_args): the flag is read by a pre-parser, in front of the
+    reference flag set of get_parser."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'],
+                     help='operands of the 7x7 convolution passes: float32 or bf16 (float32 accumulation)')
+    known, rest = pre.parse_known_args(argv)
+    return known.dtype, rest
 
 
 def create_result_dir(prefix):
@@ -136,7 +154,9 @@ def evaluate(trainer, valid, eval_shape, batchsize):
 
 def main(argv=None):
     import torch
+    dtype, argv = get_dtype_args(argv)
     args = get_args(argv)
+    args.dtype = dtype
     check_supported(args)
     st = importlib.import_module('superpixel-align_amd.segnet_train')
     segnet = importlib.import_module('superpixel-align_amd.segnet')
@@ -160,7 +180,7 @@ def main(argv=None):
     else:
         opt = st.MomentumSGD(args.lr, weight_decay=args.weight_decay)
     torch.cuda.set_device(0)
-    trainer = st.SegNetTrainer(st.init_params(0), opt, lossfun, device=0)
+    trainer = st.SegNetTrainer(st.init_params(0), opt, lossfun, device=0, dtype=args.dtype)
     it = st.ShuffledIterator(n_train, args.batchsize)
 
     result_dir = args.result_dir if args.result_dir is not None else create_result_dir(args.prefix)
@@ -172,7 +192,10 @@ def main(argv=None):
     log = []
     if args.resume is not None:
         params, state, t, lr, iteration, it_state, rnd = st.load_snapshot_state(args.resume)
-        trainer = st.SegNetTrainer(params, opt, lossfun, engine=trainer.eng)
+        snap_dtype = st.snapshot_dtype(args.resume)
+        if snap_dtype != args.dtype:
+            print('resuming a %s snapshot in %s' % (snap_dtype, args.dtype))
+        trainer = st.SegNetTrainer(params, opt, lossfun, engine=trainer.eng, dtype=args.dtype)
         opt.t = t
         if args.optimizer == 'MomentumSGD':
             opt.lr = lr
