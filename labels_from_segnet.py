@@ -52,9 +52,13 @@ def _save_figure(d, i, pred, label, out_dir):
 
 def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
                 start_index, end_index, soft_label, eval_shape,
-                save_each=False, figure=True, batchsize=4):
+                save_each=False, figure=True, batchsize=4, result_fn=None, on_labels=None):
     """labels_from_segnet.py:24-153.  With save_each=False returns {<out_dir>/<basename>: bool mask,
-    <out_dir>/<basename>_scores: float32 (2, H, W) probabilities at eval_shape}."""
+    <out_dir>/<basename>_scores: float32 (2, H, W) probabilities at eval_shape}.  result_fn: the file the JSON lines
+    are appended to (default <out_dir>/result.json; utils/run_train_rounds.py gives each labelling process its own).
+    on_labels (save_each=False): called with (key, array) for the mask and then the scores of every image, in index
+    order, instead of collecting them in the returned dict (which stays empty), so a long range needs the memory of
+    one batch only."""
     import torch
     segnet = importlib.import_module('superpixel-align_amd.segnet')
     cli = importlib.import_module('superpixel-align_amd.cli')
@@ -114,12 +118,15 @@ def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
             if save_each:
                 np.save(save_fn, pred)
                 np.save(save_fn + '_scores', pred)       # sic: the reference saves the mask under this name too
+            elif on_labels is not None:
+                on_labels(save_fn, pred)
+                on_labels(save_fn + '_scores', scores[j].astype(np.float32))
             else:
                 pred_and_scores[save_fn] = pred
                 pred_and_scores[save_fn + '_scores'] = scores[j].astype(np.float32)
             if figure:
                 _save_figure(d, i, pred, label, out_dir)
-            with open(os.path.join(out_dir, 'result.json'), 'a') as fp:
+            with open(result_fn or os.path.join(out_dir, 'result.json'), 'a') as fp:
                 result_info = {
                     'img_fn': d.img_fns[i],
                     'label_fn': d.label_fns[i],

@@ -19,6 +19,9 @@ cores (csrc/spa_segnet_train_bf16.hip): every product operand (conv input, weigh
 the products accumulate in float32, and everything else -- the float32 master weights, BatchNorm, pooling, the
 classifier, the loss and the optimizers -- is the float32 path unchanged.  `reference_loss(..., bf16_operands=True)`
 restates that step in float64.
+
+Data parallelism (train_segnet.py --data_parallel, SegNetTrainer.set_group(RankGroup())): one rank per GPU under
+torchrun, BatchNorm over the union of the ranks' batches and the mean of the ranks' gradients; see RankGroup.
 """
 import os
 import zipfile
@@ -315,11 +318,15 @@ def _functions():
             return dx, dw, None, None, None
 
     class BatchNorm(torch.autograd.Function):
-        """BN with given batch statistics over (B,H,W) of a (B,H,W,64) map; the standard backward through them"""
+        """BN with given batch statistics over (B,H,W) of a (B,H,W,64) map; the standard backward through them.
+        group (a RankGroup, data-parallel runs): the statistics are over the union of every rank's batch, so dy is
+        formed from the sums of g and g * xhat over all ranks (m = world size * B*H*W), while gamma and beta get this
+        rank's own sums: the gradient all-reduce adds them up once."""
 
         @staticmethod
-        def forward(ctx, y, gamma, beta, mean, rstd):
+        def forward(ctx, y, gamma, beta, mean, rstd, group=None):
             ctx.save_for_backward(y, gamma, mean, rstd)
+            ctx.group = group
             return (y - mean) * (rstd * gamma) + beta
 
         @staticmethod
@@ -329,8 +336,13 @@ def _functions():
             xhat = (y - mean) * rstd
             dbeta = g.sum((0, 1, 2))
             dgamma = (g * xhat).sum((0, 1, 2))
-            dy = (gamma * rstd / m) * (m * g - dbeta - xhat * dgamma)
-            return dy, dgamma, dbeta, None, None
+            if ctx.group is None:
+                dy = (gamma * rstd / m) * (m * g - dbeta - xhat * dgamma)
+            else:
+                m *= ctx.group.size
+                s = ctx.group.sum_in_rank_order(torch.stack([dbeta, dgamma]))
+                dy = (gamma * rstd / m) * (m * g - s[0] - xhat * s[1])
+            return dy, dgamma, dbeta, None, None, None
 
     return Conv7, BatchNorm
 
@@ -358,6 +370,14 @@ class SegNetTrainer(object):
         self.opt = optimizer
         self.lossfun = lossfun
         self.dtype = dtype
+        self.group = None           # a RankGroup: data-parallel steps (set_group)
+
+    def set_group(self, group):
+        """Make every step a data-parallel step over `group` (a RankGroup, or None for one process) and give every
+        rank rank 0's parameters and running statistics."""
+        self.group = group
+        if group is not None:
+            group.broadcast_(list(self.P.values()) + list(self.S.values()))
 
     def loss(self, img, t, trace=None):
         """img (B,3,H,W) float32 0..255 on the device (after augmentation, before standardisation), t the labels ->
@@ -371,15 +391,20 @@ class SegNetTrainer(object):
         P = self.P
         h, pools = img.contiguous(), []
 
+        group = self.group
+
         def bn(name, y, stats):
             m = float(y.shape[0] * y.shape[1] * y.shape[2])
+            if group is not None:
+                stats = group.sum_in_rank_order(stats)
+                m *= group.size
             mean = stats[0] / m
             var = (stats[1] / m - mean * mean).clamp_min(0.0)
             rstd = (1.0 / torch.sqrt(var + BN_EPS)).float()
             with torch.no_grad():
                 bn_update(self.S[name + '_bn/avg_mean'], self.S[name + '_bn/avg_var'], mean.float(), var.float(), m)
             self.N[name] += 1
-            return BatchNorm.apply(y, P[name + '_bn/gamma'], P[name + '_bn/beta'], mean.float(), rstd)
+            return BatchNorm.apply(y, P[name + '_bn/gamma'], P[name + '_bn/beta'], mean.float(), rstd, group)
 
         for name in ENCODERS:
             y, stats = Conv7.apply(h, pack_w(P[name + '/W']), None, self.eng, self.dtype == 'bf16')
@@ -405,6 +430,8 @@ class SegNetTrainer(object):
             grads = dict(zip(leaves.keys(), torch.autograd.grad(loss, list(leaves.values()))))
         finally:
             self.P = saved
+        if self.group is not None:
+            grads = self.group.mean_gradients(grads)
         with torch.no_grad():
             self.opt.update(self.P, grads)
         return float(loss.detach())
@@ -419,6 +446,136 @@ class SegNetTrainer(object):
     def predictor(self, pred_shape=None):
         """The inference network (BN folded from the running statistics) on the same engine."""
         return segnet.SegNetBasic(self.params_numpy(), pred_shape, engine=self.eng)
+
+
+# ------------------------------------------------------------------------------- data parallelism
+class RankGroup(object):
+    """The collectives of a data-parallel run (train_segnet.py --data_parallel) over torch.distributed's initialised
+    default group.  A step on N ranks with b images each computes the gradient of L = (1/N) sum_r L_r, L_r the loss of
+    rank r's own batch, with BatchNorm statistics over the union of the N batches (what ChainerMN's
+    MultiNodeBatchNormalization and create_multi_node_optimizer intend); with no ignored labels that is the step of
+    one process on the N*b images.  Per step:
+      * every BN forward: the kernel's (sum y, sum y^2), float64 (2, 64), summed over the ranks (sum_in_rank_order);
+        mean, variance and bn_update's unbiased factor use m = N*B*H*W;
+      * every BN backward: (sum g, sum g*xhat) summed the same way for dy; gamma and beta get this rank's LOCAL sums
+        as their gradients (the global ones would be counted N times by the all-reduce below);
+      * all parameter gradients flattened into one float32 bucket, one all_reduce(SUM), divided by N; the optimizer
+        (weight decay, ExponentialShift, Adam's bias correction) then runs identically on every rank.
+    Collectives run on the backend's device: the rank's GPU for nccl (RCCL), host copies for gloo (the convention of
+    dist.gather_records).  Every per-rank computation is the one-process path unchanged, so one rank reproduces the
+    one-process bits."""
+
+    def __init__(self):
+        import torch.distributed as dist
+        torch = _torch()
+        self.dist = dist
+        self.rank, self.size = dist.get_rank(), dist.get_world_size()
+        self.device = (torch.device('cuda', torch.cuda.current_device()) if dist.get_backend() == 'nccl'
+                       else torch.device('cpu'))
+
+    def sum_in_rank_order(self, t):
+        """t summed over the ranks, on t's device: an all_gather, then parts[0] + parts[1] + ... in rank order, so
+        every rank holds the same bits whatever algorithm the collective uses."""
+        torch = _torch()
+        x = t.detach().to(self.device).contiguous()
+        parts = [torch.empty_like(x) for _ in range(self.size)]
+        self.dist.all_gather(parts, x)
+        total = parts[0]
+        for p in parts[1:]:
+            total = total + p
+        return total.to(t.device)
+
+    def mean_gradients(self, grads):
+        """{name: gradient} -> the mean over the ranks: one all_reduce(SUM) of one flat bucket, divided by N."""
+        torch = _torch()
+        keys = list(grads)
+        flat = torch.cat([grads[k].reshape(-1) for k in keys]).to(self.device)
+        self.dist.all_reduce(flat, op=self.dist.ReduceOp.SUM)
+        flat /= self.size
+        flat = flat.to(grads[keys[0]].device)
+        out, o = {}, 0
+        for k in keys:
+            n = grads[k].numel()
+            out[k] = flat[o:o + n].view_as(grads[k])
+            o += n
+        return out
+
+    def broadcast_(self, tensors, src=0):
+        """rank src's values into `tensors` (float32, one device) on every rank: one broadcast of a flat copy."""
+        torch = _torch()
+        flat = torch.cat([t.reshape(-1) for t in tensors]).to(self.device)
+        self.dist.broadcast(flat, src)
+        o = 0
+        for t in tensors:
+            n = t.numel()
+            t.copy_(flat[o:o + n].view_as(t))
+            o += n
+
+    def mean_over_ranks(self, report):
+        """{key: number} -> {key: the mean of the ranks' values} (create_multi_node_evaluator: a mean of per-rank
+        metrics, not a pooled confusion)."""
+        torch = _torch()
+        keys = sorted(report)
+        total = self.sum_in_rank_order(torch.tensor([float(report[k]) for k in keys], dtype=torch.float64))
+        return {k: float(v) / self.size for k, v in zip(keys, total.tolist())}
+
+    def gather_objects(self, obj):
+        """one picklable object per rank -> the list over ranks, on every rank"""
+        out = [None] * self.size
+        self.dist.all_gather_object(out, obj)
+        return out
+
+    def barrier(self):
+        self.dist.barrier()
+
+
+def shard_indices(n, n_ranks, rank, shuffle=True, seed=0):
+    """The examples of `rank` among n_ranks, as chainermn.scatter_dataset splits a dataset of n: with shuffle, a
+    permutation from its own np.random.RandomState(seed) (numpy's global stream is not consumed), else 0..n-1; rank r
+    takes order[n*r//N : n*r//N + ceil(n/N)], so the last rank ends at n, every rank gets ceil(n/N) examples and the
+    shards overlap where N does not divide n.  One rank keeps the whole set in its order (the one-process run)."""
+    if n_ranks == 1:
+        return np.arange(n)
+    order = np.random.RandomState(seed).permutation(n) if shuffle else np.arange(n)
+    lo = n * rank // n_ranks
+    return order[lo:lo + -(-n // n_ranks)]
+
+
+DP_KEY = 'extensions/data_parallel/'      # data-parallel snapshots: world size, every rank's iterator and numpy state
+
+
+def rank_state(iterator):
+    """this rank's iterator state and numpy random state, as a data-parallel snapshot stores them per rank"""
+    st = np.random.get_state()
+    out = {'iterator/' + k: np.asarray(v) for k, v in iterator.state().items()}
+    out.update({'np_random/keys': st[1], 'np_random/pos': np.asarray(st[2]), 'np_random/has_gauss': np.asarray(st[3]),
+                'np_random/cached_gaussian': np.asarray(st[4])})
+    return out
+
+
+def data_parallel_extra(states):
+    """every rank's rank_state (rank order) -> the extra snapshot entries of a data-parallel run"""
+    d = {DP_KEY + 'world_size': np.asarray(len(states))}
+    for r, s in enumerate(states):
+        for k, v in s.items():
+            d['%srank%d/%s' % (DP_KEY, r, k)] = v
+    return d
+
+
+def snapshot_world_size(path):
+    """The number of ranks that wrote a snapshot, or None for a one-process snapshot."""
+    with np.load(path) as z:
+        return int(z[DP_KEY + 'world_size']) if DP_KEY + 'world_size' in z.files else None
+
+
+def load_rank_state(path, rank):
+    """-> (iterator state, np random state) of `rank` from a data-parallel snapshot"""
+    pre = '%srank%d/' % (DP_KEY, rank)
+    with np.load(path) as z:
+        it_state = {f[len(pre + 'iterator/'):]: np.asarray(z[f]) for f in z.files if f.startswith(pre + 'iterator/')}
+        rnd = ('MT19937', np.asarray(z[pre + 'np_random/keys']), int(z[pre + 'np_random/pos']),
+               int(z[pre + 'np_random/has_gauss']), float(z[pre + 'np_random/cached_gaussian']))
+    return it_state, rnd
 
 
 # ------------------------------------------------------------------------------- snapshots

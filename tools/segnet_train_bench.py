@@ -6,6 +6,10 @@ forward FLOPs, wgrad too) against the matrix peak of the dtype: 157.3 TF float32
 Random weights and inputs: the time does not depend on the values.
 
   python tools/segnet_train_bench.py [--dtype fp32|bf16] [--batch 4] [--iters 10] [--out profiles/segnet_train_bench_b4.json]
+
+--data_parallel: the step of a data-parallel rank (segnet_train.RankGroup: BN statistics and gradients exchanged).
+Under SPA_DIST_FORCE=1 on one GPU that is one RCCL rank, which times the exchanges' own cost; under torchrun one rank
+of many.
 """
 import argparse
 import importlib
@@ -44,12 +48,21 @@ def main():
     ap.add_argument('--width', type=int, default=1024)
     ap.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'])
     ap.add_argument('--out', default=None)
+    ap.add_argument('--data_parallel', action='store_true')
     a = ap.parse_args()
     B, H, W = a.batch, a.height, a.width
     sfx = '_bf16' if a.dtype == 'bf16' else ''
     peak = PEAK_TF[a.dtype]
-    torch.cuda.set_device(0)
-    eng = engine.Engine(0)
+    group = None
+    if a.data_parallel:
+        dist = importlib.import_module('superpixel-align_amd.dist')
+        dist.init()
+        if torch.distributed.is_initialized():
+            group = st.RankGroup()
+        eng = engine.default_engine()
+    else:
+        torch.cuda.set_device(0)
+        eng = engine.Engine(0)
     fwd, dgrad, wgrad = (getattr(eng, 'segnet_train_' + k + sfx) for k in ('forward', 'dgrad', 'wgrad'))
     flops = segnet.layer_flops(H, W)
     g = torch.Generator(device='cuda').manual_seed(0)
@@ -85,6 +98,7 @@ def main():
     # the whole step
     tr = st.SegNetTrainer(st.init_params(0), st.MomentumSGD(0.01, weight_decay=0.0005), st.softmax_cross_entropy,
                           engine=eng, dtype=a.dtype)
+    tr.set_group(group)
     img = torch.rand((B, 3, H, W), generator=g, device='cuda') * 255
     t = torch.randint(0, 2, (B, H, W), generator=g, device='cuda')
     tr.step(img, t)
@@ -104,6 +118,9 @@ def main():
     else:
         out.update({'dtype': 'bf16', 'peak_tflops_bf16_matrix': peak, 'conv_share_of_peak': out['conv_tflops'] / peak,
                     'step_outside_conv_kernels_ms': step_ms - kern_ms})
+    if a.data_parallel:
+        out.update({'data_parallel': True, 'world_size': group.size if group is not None else 1,
+                    'backend': torch.distributed.get_backend() if group is not None else None})
     out.update({'layers': rows, 'device': torch.cuda.get_device_name(0)})
     s = json.dumps(out, indent=2)
     print(s)

@@ -10,7 +10,8 @@ Outputs in the result directory (create_result_dir(prefix), or --result_dir):
                          val/main/iou/non_road, val/main/miou, val_/main/precision, val_/main/recall, val_/main/FP, FN
   snapshot_iter_<N>      every --val_interval: the npz labels_from_segnet.py reads (updater/model:main/predictor/...)
                          plus the optimizer, iteration, lr and iterator state that --resume reads
-Only --model basic, one process, and units of 'iteration' (an 'epoch' interval is converted with the dataset size).
+Only --model basic; one process unless --data_parallel is given.  An 'epoch' interval is converted to iterations
+with the size of the (per-rank) training set.
 
 --dtype {fp32,bf16} (this implementation's addition, parsed in front of the reference flags; default fp32): bf16 runs
 every 7x7 convolution pass of a training step on the bf16 matrix cores, with float32 accumulation, float32 master
@@ -18,6 +19,15 @@ weights, BatchNorm and optimizer.  The dtype goes into args.txt and every snapsh
 the snapshot's own dtype, and a float32 snapshot may also be resumed in bf16 or the other way round (the weights and the
 optimizer state are float32 in both).  Validation always runs the float32 inference network, and labels_from_segnet.py
 reads the snapshots of either dtype.
+
+--data_parallel (also parsed in front of the reference flags): run as one rank of a torchrun launch (RANK, WORLD_SIZE,
+LOCAL_RANK; dist.init binds the rank's GPU), what the reference does under mpiexec with ChainerMN.  A step computes
+the gradient of the mean of the ranks' losses with BatchNorm over all ranks' batches (segnet_train.RankGroup).  Rank
+r seeds random, numpy and torch with r; the training set is split by segnet_train.shard_indices (chainermn's
+scatter_dataset with shuffle), the validation set into contiguous shards, and every reported validation metric is the
+mean of the ranks' values.  Only rank 0 writes args.txt (with data_parallel and world_size), the log (main/loss is its
+own) and the snapshots, which add the world size and every rank's iterator and numpy state; --resume continues bit
+for bit with the same world size and refuses another one.  One rank computes the one-process run's bits.
 """
 import argparse
 import importlib
@@ -91,6 +101,18 @@ def get_dtype_args(argv=None):
     return known.dtype, rest
 
 
+def get_pre_args(argv=None):
+    """-> (namespace of this implementation's flags, the remaining arguments for get_args): --dtype (get_dtype_args)
+    and --data_parallel, read by one pre-parser in front of the reference flag set of get_parser."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'],
+                     help='operands of the 7x7 convolution passes: float32 or bf16 (float32 accumulation)')
+    pre.add_argument('--data_parallel', action='store_true', default=False,
+                     help='run as one rank of a torchrun launch (RANK / WORLD_SIZE / LOCAL_RANK)')
+    return pre.parse_known_args(argv)
+
+
 def create_result_dir(prefix):
     """<prefix>_<time>_<i> for the first i >= 0 that does not exist yet; copies this script into it."""
     stamp = time.strftime('%Y-%m-%d_%H-%M-%S')
@@ -105,14 +127,16 @@ def create_result_dir(prefix):
 
 
 def check_supported(args):
-    """The refusals: the VGG-style 'normal' SegNet (segnet.load_train_args' message) and multi-rank launches."""
+    """The refusals: the VGG-style 'normal' SegNet (segnet.load_train_args' message) and multi-rank launches without
+    --data_parallel."""
     if args.model != 'basic':
         raise ValueError("--model '%s' is not supported: only SegNet-Basic ('basic') is implemented%s"
                          % (args.model, " (the VGG-style 'normal' SegNet is not)" if args.model == 'normal' else ''))
     ws = int(os.environ.get('WORLD_SIZE', os.environ.get('OMPI_COMM_WORLD_SIZE', '1')))
-    if ws > 1:
-        raise RuntimeError('train_segnet.py runs in one process only (WORLD_SIZE=%d): the multi-node BatchNorm of a '
-                           'multi-rank run (cross-rank batch statistics) is not implemented' % ws)
+    if ws > 1 and not getattr(args, 'data_parallel', False):
+        raise RuntimeError('train_segnet.py runs in one process only unless --data_parallel is given (WORLD_SIZE=%d): '
+                           'a multi-rank launch needs the cross-rank BatchNorm and gradient all-reduce of '
+                           '--data_parallel' % ws)
 
 
 def _iterations(interval, n_data, batchsize):
@@ -124,16 +148,18 @@ def _iterations(interval, n_data, batchsize):
     raise ValueError('unknown interval unit %r' % unit)
 
 
-def evaluate(trainer, valid, eval_shape, batchsize):
-    """SemanticSegmentationEvaluator + PrecisionRecallEvaluator over the validation set with the inference network
-    (BN folded from the running statistics), predicting as labels_from_segnet.py does -> the report entries."""
+def evaluate(trainer, valid, eval_shape, batchsize, indices=None):
+    """SemanticSegmentationEvaluator + PrecisionRecallEvaluator over the validation set (or its examples `indices`)
+    with the inference network (BN folded from the running statistics), predicting as labels_from_segnet.py does ->
+    the report entries."""
     import torch
     model = trainer.predictor(eval_shape)
     eng = trainer.eng
     in_shape = tuple(int(v) for v in valid.resize_shape)
+    indices = list(range(len(valid))) if indices is None else [int(i) for i in indices]
     conf = np.zeros(4, np.int64)                                    # TN, FP, FN, TP
-    for lo in range(0, len(valid), batchsize):
-        raws = [valid.get_raw(i) for i in range(lo, min(lo + batchsize, len(valid)))]
+    for lo in range(0, len(indices), batchsize):
+        raws = [valid.get_raw(i) for i in indices[lo:lo + batchsize]]
         for img, label in raws:
             u8 = torch.from_numpy(np.ascontiguousarray(img.transpose(1, 2, 0))[None]).to(eng.device)
             x = eng.resize_cvcubic_u8(u8.contiguous(), in_shape)
@@ -152,48 +178,88 @@ def evaluate(trainer, valid, eval_shape, batchsize):
             'val_/main/precision': prec, 'val_/main/recall': rec, 'val_/main/FP': FP, 'val_/main/FN': FN}
 
 
+def resume_check(snapshot_world_size, world_size):
+    """The refusal of a resume across world sizes: a data-parallel snapshot records its world size and every rank's
+    iterator, a one-process snapshot (None) only one iterator."""
+    if (snapshot_world_size or 1) != world_size:
+        raise RuntimeError('--resume: the snapshot was written by %s, this run has %d rank(s); resume with the world '
+                           'size that wrote it' % ('%d rank(s)' % snapshot_world_size if snapshot_world_size
+                                                   else 'one process', world_size))
+
+
 def main(argv=None):
     import torch
-    dtype, argv = get_dtype_args(argv)
+    pre, argv = get_pre_args(argv)
     args = get_args(argv)
-    args.dtype = dtype
+    args.dtype = pre.dtype
+    dp = pre.data_parallel
+    if dp:
+        args.data_parallel = True                  # args.txt records it with the world size; one-process runs unchanged
     check_supported(args)
     st = importlib.import_module('superpixel-align_amd.segnet_train')
     segnet = importlib.import_module('superpixel-align_amd.segnet')
 
-    random.seed(0)
-    np.random.seed(0)
-    torch.manual_seed(0)
-    print(json.dumps(vars(args), indent=4, sort_keys=True))
+    group = None
+    rank, ws = 0, 1
+    eng = None
+    if dp:
+        dist = importlib.import_module('superpixel-align_amd.dist')
+        rank, ws, _ = dist.init()                  # binds this rank's GPU; a process group for ws > 1 or SPA_DIST_FORCE
+        import torch.distributed
+        if torch.distributed.is_initialized():
+            group = st.RankGroup()
+        eng = importlib.import_module('superpixel-align_amd.engine').default_engine()
+        args.world_size = ws
+    else:
+        torch.cuda.set_device(0)
+
+    snap_ws = None
+    if args.resume is not None:
+        snap_ws = st.snapshot_world_size(args.resume)
+        resume_check(snap_ws, ws)                  # before anything is written
+
+    random.seed(rank)                              # the reference seeds by intra_rank
+    np.random.seed(rank)
+    torch.manual_seed(rank)
+    if rank == 0:
+        print(json.dumps(vars(args), indent=4, sort_keys=True))
 
     soft_label = args.use_soft_label or args.use_mse
     train = st.ZippedEstimatedCityscapesDataset(args.train_img_zip, args.train_label_zip, args.input_shape,
                                                 args.random, soft_label)
     n_train = len(train) if args.n_use_data is None else min(args.n_use_data, len(train))
-    print('train dataset:', n_train)
     valid = segnet.ZippedCityscapesRoadDataset(args.val_img_zip, args.val_label_zip, args.input_shape)
-    print('valid dataset:', len(valid))
+    # scatter_dataset: the training set shuffled into ws shards, the validation set in contiguous ones
+    train_ids = st.shard_indices(n_train, ws, rank, shuffle=True)
+    valid_ids = st.shard_indices(len(valid), ws, rank, shuffle=False)
+    if rank == 0:
+        print('train dataset:', n_train)
+        print('valid dataset:', len(valid))
 
     lossfun = st.loss_function(args.use_soft_label, args.use_mse)
     if args.optimizer == 'Adam':
         opt = st.Adam()
     else:
         opt = st.MomentumSGD(args.lr, weight_decay=args.weight_decay)
-    torch.cuda.set_device(0)
-    trainer = st.SegNetTrainer(st.init_params(0), opt, lossfun, device=0, dtype=args.dtype)
-    it = st.ShuffledIterator(n_train, args.batchsize)
+    device = torch.cuda.current_device()
+    trainer = st.SegNetTrainer(st.init_params(0), opt, lossfun, engine=eng, device=device, dtype=args.dtype)
+    it = st.ShuffledIterator(len(train_ids), args.batchsize)
 
-    result_dir = args.result_dir if args.result_dir is not None else create_result_dir(args.prefix)
-    os.makedirs(result_dir, exist_ok=True)
-    with open(os.path.join(result_dir, 'args.txt'), 'w') as fp:
-        json.dump(vars(args), fp, indent=4, sort_keys=True)
+    result_dir = None
+    if rank == 0:
+        result_dir = args.result_dir if args.result_dir is not None else create_result_dir(args.prefix)
+        os.makedirs(result_dir, exist_ok=True)
+        with open(os.path.join(result_dir, 'args.txt'), 'w') as fp:
+            json.dump(vars(args), fp, indent=4, sort_keys=True)
 
     iteration = 0
     log = []
     if args.resume is not None:
         params, state, t, lr, iteration, it_state, rnd = st.load_snapshot_state(args.resume)
+        if snap_ws is not None:
+            it_state, rnd = st.load_rank_state(args.resume, rank)
         snap_dtype = st.snapshot_dtype(args.resume)
-        if snap_dtype != args.dtype:
+        if snap_dtype != args.dtype and rank == 0:
             print('resuming a %s snapshot in %s' % (snap_dtype, args.dtype))
         trainer = st.SegNetTrainer(params, opt, lossfun, engine=trainer.eng, dtype=args.dtype)
         opt.t = t
@@ -203,18 +269,20 @@ def main(argv=None):
         it.load(it_state)
         np.random.set_state(rnd)
         log_fn = os.path.join(os.path.dirname(os.path.abspath(args.resume)), 'log')
-        if os.path.exists(log_fn):
+        if rank == 0 and os.path.exists(log_fn):
             log = [e for e in json.load(open(log_fn)) if e['iteration'] <= iteration]
+    trainer.set_group(group)                       # every rank starts from rank 0's parameters
 
-    stop = _iterations(args.train_limit, n_train, args.batchsize)
-    log_every = _iterations(args.log_interval, n_train, args.batchsize)
-    val_every = _iterations(args.val_interval, n_train, args.batchsize)
+    # epoch units count the examples of this rank's shard, as the reference's per-rank iterator does
+    stop = _iterations(args.train_limit, len(train_ids), args.batchsize)
+    log_every = _iterations(args.log_interval, len(train_ids), args.batchsize)
+    val_every = _iterations(args.val_interval, len(train_ids), args.batchsize)
     decay = args.decay_iteration if args.optimizer == 'MomentumSGD' else 0
     dev = trainer.eng.device
     losses = []
     t0 = time.time()
     while iteration < stop:
-        ids = it.next_indices()
+        ids = train_ids[it.next_indices()]
         batch = [train.get_example(i) for i in ids]
         img = torch.from_numpy(np.stack([b[0] for b in batch])).to(dev)
         lab = torch.from_numpy(np.stack([b[1] for b in batch])).to(dev)
@@ -225,21 +293,31 @@ def main(argv=None):
             opt.lr *= 0.1                                            # ExponentialShift('lr', 0.1)
         report = {}
         if iteration % val_every == 0:
-            report.update(evaluate(trainer, valid, args.eval_shape, args.batchsize))
+            report.update(evaluate(trainer, valid, args.eval_shape, args.batchsize, valid_ids))
+            if group is not None:
+                report = group.mean_over_ranks(report)               # create_multi_node_evaluator: mean over ranks
         if iteration % log_every == 0:
             entry = {'epoch': it.epoch, 'iteration': iteration, 'main/loss': float(np.mean(losses)),
                      'lr': lr_used, 'elapsed_time': time.time() - t0}
             entry.update(report)
-            log.append(entry)
             losses = []
-            with open(os.path.join(result_dir, 'log'), 'w') as fp:
-                json.dump(log, fp, indent=4)
-            print(json.dumps({k: entry.get(k) for k in ('iteration', 'main/loss', 'val/main/iou/road',
-                                                        'val_/main/precision', 'val_/main/recall', 'lr',
-                                                        'elapsed_time')}))
+            if rank == 0:
+                log.append(entry)
+                with open(os.path.join(result_dir, 'log'), 'w') as fp:
+                    json.dump(log, fp, indent=4)
+                print(json.dumps({k: entry.get(k) for k in ('iteration', 'main/loss', 'val/main/iou/road',
+                                                            'val_/main/precision', 'val_/main/recall', 'lr',
+                                                            'elapsed_time')}))
         if iteration % val_every == 0:
-            st.save_snapshot(os.path.join(result_dir, 'snapshot_iter_{}'.format(iteration)), trainer, iteration,
-                             opt.lr, it.state())
+            extra = None
+            if dp:
+                states = group.gather_objects(st.rank_state(it)) if group is not None else [st.rank_state(it)]
+                extra = st.data_parallel_extra(states)
+            if rank == 0:
+                st.save_snapshot(os.path.join(result_dir, 'snapshot_iter_{}'.format(iteration)), trainer, iteration,
+                                 opt.lr, it.state(), extra)
+    if group is not None:
+        group.barrier()                            # no rank leaves before rank 0's last snapshot is written
     return result_dir
 
 
