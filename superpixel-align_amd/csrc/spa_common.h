@@ -121,7 +121,7 @@ struct spa_ctx {
     size_t conn_claim_bytes;
     int upd_wg_per_cu, upd_wg_per_cu8;
     int slic_force_general;      // SPA_SLIC_GENERAL=1 at context creation: spa_slic_core takes the general kernels
-    int zero_line_ready, conv_attr_done, conv32_attr_done, fz_attr_done, gemm16_attr_done, gemm16s_attr_done, nprng_attr_done, conv_stag_attr_done;
+    int zero_line_ready, conv_attr_done, conv32_attr_done, fz_attr_done, gemm16_attr_done, gemm16s_attr_done, nprng_attr_done;
     int rng_seeded;
     int ws_generation;             // counts workspace re-allocations (spa_ws_generation: captured graphs hold workspace addresses)
     int dbg_slic_ldsx;             // spa_debug_set key 2 (diagnostic builds: the reproducer variant of k_slic_assign)

@@ -35,14 +35,13 @@
 //     peak (the chip lowers its clock under dense bf16 MFMA on random data: MI355X_MICROARCH.md, DVFS give-back),
 //     so the kernel is at ~0.9 of what its loop can deliver.
 #include "spa_common.h"
-#include <stdlib.h>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// output channels per workgroup: template parameter BM = 256 (2 x 4 waves of 128 x 64), 128 (2 x 4 waves of
-// 64 x 64) or 64 (1 x 8 waves of 64 x 32) — the narrow tiles serve the 64/128-channel layers, which are bound by
-// their activations' HBM traffic, not by the matrix pipe
+// output channels per workgroup: template parameter BM = 256 (2 x 4 waves of 128 x 64; launched as k_conv3x3_bf16_stag
+// below), 128 (2 x 4 waves of 64 x 64) or 64 (1 x 8 waves of 64 x 32) — the narrow tiles serve the 64/128-channel layers,
+// which are bound by their activations' HBM traffic, not by the matrix pipe
 #define CV_BN 256            // pixels per workgroup
 #define CV_BK 64             // K step (input channels of one tap)
 #define CV_THREADS 512
@@ -387,39 +386,23 @@ extern "C" int spa_conv3x3_bf16(spa_ctx *ctx, const void *x, int32_t B, int32_t 
     SPA_ARG(total < (1ll << 31));
     const size_t lds = 2 * (size_t)CV_TILE_BYTES + 2 * (size_t)CV_XSEG_BYTES;
     if (!ctx->conv_attr_done) {
-#define CV_ATTR(R, M) SPA_HIP(hipFuncSetAttribute((const void *)k_conv3x3_bf16<R, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-        CV_ATTR(0, 256); CV_ATTR(1, 256); CV_ATTR(0, 128); CV_ATTR(1, 128); CV_ATTR(0, 64); CV_ATTR(1, 64);
+#define CV_ATTR(K, R, M) SPA_HIP(hipFuncSetAttribute((const void *)K<R, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+        CV_ATTR(k_conv3x3_bf16_stag, 0, 256); CV_ATTR(k_conv3x3_bf16_stag, 1, 256);
+        CV_ATTR(k_conv3x3_bf16, 0, 128); CV_ATTR(k_conv3x3_bf16, 1, 128); CV_ATTR(k_conv3x3_bf16, 0, 64); CV_ATTR(k_conv3x3_bf16, 1, 64);
 #undef CV_ATTR
         ctx->conv_attr_done = 1;
     }
     SpaProfScope prof_(ctx, PROF_DRN_CONV, s);
-    // SPA_CONV16_STAGGER (read once): unset / 1 = the half-period-lag kernel for the 256-channel tile (512 -> 512, 30 images: 4.14
-    // against 4.48 ms with the residual, 3.99 against 4.39 without; 256 -> 512 2.24 against 2.45; 256 -> 256 1.31 against 1.39:
-    // tools/conv16_ab.py, digests equal), 0 = round 1's kernel (also the narrow tiles')
-    static const int stag = getenv("SPA_CONV16_STAGGER") ? atoi(getenv("SPA_CONV16_STAGGER")) : 1;
-    if (stag && bm == 256) {
-        if (!ctx->conv_stag_attr_done) {
-            SPA_HIP(hipFuncSetAttribute((const void *)k_conv3x3_bf16_stag<0, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            SPA_HIP(hipFuncSetAttribute((const void *)k_conv3x3_bf16_stag<1, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            ctx->conv_stag_attr_done = 1;
-        }
-#define CV_LAUNCH_S(R)                                                                                                   \
-    hipLaunchKernelGGL((k_conv3x3_bf16_stag<R, 256>), dim3((unsigned)total), dim3(CV_THREADS), lds, s, (const __bf16 *)x, \
-                       (const __bf16 *)wt, bias, (const __bf16 *)residual, (__bf16 *)y, (const char *)zero, B, H, W,    \
-                       Cin, Cout, dilation, relu, xtiles, ntiles, (int)total)
-        if (residual) CV_LAUNCH_S(1); else CV_LAUNCH_S(0);
-#undef CV_LAUNCH_S
-        SPA_LAUNCH_CHECK();
-        return SPA_OK;
-    }
-#define CV_LAUNCH(R, M)                                                                                                  \
-    hipLaunchKernelGGL((k_conv3x3_bf16<R, M>), dim3((unsigned)total), dim3(CV_THREADS), lds, s, (const __bf16 *)x,       \
+    // the 256-channel tile runs the half-period-lag kernel (against k_conv3x3_bf16 at that tile, same bits: 512 -> 512, 30 images,
+    // 4.14 against 4.48 ms with the residual, 3.99 against 4.39 without; 256 -> 512 2.24 against 2.45; 256 -> 256 1.31 against 1.39)
+#define CV_LAUNCH(K, R, M)                                                                                               \
+    hipLaunchKernelGGL((K<R, M>), dim3((unsigned)total), dim3(CV_THREADS), lds, s, (const __bf16 *)x,                    \
                        (const __bf16 *)wt, bias, (const __bf16 *)residual, (__bf16 *)y, (const char *)zero, B, H, W,    \
                        Cin, Cout, dilation, relu, xtiles, ntiles, (int)total)
     if (residual) {
-        if (bm == 256) CV_LAUNCH(1, 256); else if (bm == 128) CV_LAUNCH(1, 128); else CV_LAUNCH(1, 64);
+        if (bm == 256) CV_LAUNCH(k_conv3x3_bf16_stag, 1, 256); else if (bm == 128) CV_LAUNCH(k_conv3x3_bf16, 1, 128); else CV_LAUNCH(k_conv3x3_bf16, 1, 64);
     } else {
-        if (bm == 256) CV_LAUNCH(0, 256); else if (bm == 128) CV_LAUNCH(0, 128); else CV_LAUNCH(0, 64);
+        if (bm == 256) CV_LAUNCH(k_conv3x3_bf16_stag, 0, 256); else if (bm == 128) CV_LAUNCH(k_conv3x3_bf16, 0, 128); else CV_LAUNCH(k_conv3x3_bf16, 0, 64);
     }
 #undef CV_LAUNCH
     SPA_LAUNCH_CHECK();

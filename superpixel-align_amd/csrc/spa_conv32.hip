@@ -15,7 +15,6 @@
 // for the same bytes of operands, so a K step here is ~16 000 MFMA cycles per SIMD against one workgroup barrier
 // and 43 KB of loads: the loop is MFMA bound by a wide margin.
 #include "spa_common.h"
-#include <stdlib.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
@@ -46,7 +45,7 @@ __global__ __launch_bounds__(C32_THREADS) void k_conv3x3_f32(const float *__rest
                                                              const char *__restrict__ zero_line, int B, int H, int W,
                                                              int Cin, int Cout, int dil, int relu, int xtiles,
                                                              int ntiles, int total_tiles, int zcount, long long xz,
-                                                             long long wz, long long yz, int late_prefetch,
+                                                             long long wz, long long yz,
                                                              const unsigned *__restrict__ amax_in = nullptr,
                                                              unsigned *__restrict__ amax_out = nullptr, float inv_t = 1.f,
                                                              int Hi = 0, int Wi = 0, float *__restrict__ Y2 = nullptr, int csplit = 0)
@@ -231,6 +230,8 @@ __global__ __launch_bounds__(C32_THREADS) void k_conv3x3_f32(const float *__rest
     __syncthreads();
     // (dxi, kc, dyi) of step t and the segment buffer of its group, carried incrementally
     int dxi = TAPS == 9 ? 0 : 1, kc = 0, dyi = TAPS == 9 ? 0 : 1, g = 0, xcur = px_par;
+    // (not peeled: a separate copy of the last K step doubles the 1x1 forms' loop and spills the 256-channel one)
+#pragma clang loop unroll(disable)
     for (int t = 0; t < nk; ++t) {
         const int cur = (t + pw_par) & 1;
         // step t + 1 and group g + 1
@@ -243,20 +244,12 @@ __global__ __launch_bounds__(C32_THREADS) void k_conv3x3_f32(const float *__rest
         // (the loads of the next K step go out in one burst: spreading them between the MFMA groups was
         // measured 20 % slower — every global_load_lds re-programs M0 and breaks the MFMA stream; issuing the next group's
         // pixel thirds AFTER the step's wait, so that no wait covers an HBM load of the same step, was 4-6 % slower too)
-#ifdef SPA_C32_FIXED_ADDR          // timing experiment (wrong numbers): step-invariant staging addresses, so that their arithmetic leaves the loop
-        if (t + 1 < nk) stage_w(0, 0, cur ^ 1);
-        if (g + 1 < ngroups) {
-            if (TAPS == 9) stage_x(1, 0, dxi, xcur ^ 1);
-            else stage_x1(0, xcur ^ 1);
-        }
-#else
         if (t + 1 < nk) stage_w(TAPS == 9 ? ndyi * 3 + ndxi : 0, nkc, cur ^ 1);
         if (g + 1 < ngroups) {
             if (TAPS == 9) stage_x(gdyi, gkc, dxi, xcur ^ 1);
             else stage_x1(g + 1, xcur ^ 1);
         }
-#endif
-        if (t + 1 == nk && !late_prefetch) {
+        if (t + 1 == nk) {
             // LAST K step of the tile: nothing of this tile is left to load and the other buffer of each pair is
             // free, so the NEXT tile's first K step is staged now and travels under this step's matrix work (staged
             // after the loop it cost its full latency with the matrix pipe idle: ~7 us per tile, 5 % of a 16-step
@@ -347,17 +340,6 @@ __global__ __launch_bounds__(C32_THREADS) void k_conv3x3_f32(const float *__rest
 
     pw_par = (pw_par + nk) & 1;
     px_par = (px_par + ngroups) & 1;
-    if (late_prefetch) {            // A/B switch (SPA_CONV32_LATE_PREFETCH=1): stage the next tile only now
-        e_row = row_id; e_x0 = x0; e_n0 = n0; e_y = ybase; e_r = rbase;
-        vid += gridDim.x;
-        more = vid < all_tiles;
-        if (more) {
-            locate(vid);
-            stage_w(0, 0, pw_par);
-            if (TAPS == 1) { locate_rows(); stage_x1(0, px_par); }
-            else { locate_x(); stage_x(0, 0, 0, px_par); stage_x(0, 0, 1, px_par); stage_x(0, 0, 2, px_par); }
-        }
-    }
     // ---- epilogue: lane holds channels c..c+3 (c = tile channel base + (lane>>4)*4) of pixel (lane & 15)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -432,10 +414,9 @@ static int conv_f32_launch(spa_ctx *ctx, const float *x, int32_t B, int32_t H, i
     // per matrix instruction: 1.53 vs 1.69 ms on the 64 -> 64 layer of 30 images — where a row fills 256-pixel tiles to 80 %)
     const bool wide64 = split && bm == 64 && (long long)((W + 255) / 256) * 256 * 4 <= 5ll * W;
     // (round 5: 512 pixels per tile where a row fills them — every wave then owns 64 channels x 64 pixels, 16 LDS fragment reads per
-    // 48 matrix instructions instead of 12 per 24; one workgroup per CU, 150 KB of LDS.  SPA_CONV32_BN512=0: the 256-pixel tile)
-    static const int bn512_on = getenv("SPA_CONV32_BN512") ? atoi(getenv("SPA_CONV32_BN512")) : 1;
-    const bool wide512 = split && bm == 64 && TAPS == 9 && bn512_on && (long long)((W + 511) / 512) * 512 * 4 <= 5ll * W;
-    const int bn = wide512 ? 512 : (bm == 256 || wide64 || getenv("SPA_CONV32_BN256") ? 256 : 128);
+    // 48 matrix instructions instead of 12 per 24; one workgroup per CU, 150 KB of LDS)
+    const bool wide512 = split && bm == 64 && TAPS == 9 && (long long)((W + 511) / 512) * 512 * 4 <= 5ll * W;
+    const int bn = wide512 ? 512 : (bm == 256 || wide64 ? 256 : 128);
     const int xtiles = (W + bn - 1) / bn, ntiles = Cout / bm;
     const long long total = (long long)B * H * xtiles * ntiles;
     SPA_ARG(total < (1ll << 31));
@@ -449,8 +430,7 @@ static int conv_f32_launch(spa_ctx *ctx, const float *x, int32_t B, int32_t H, i
     if (!(ctx->conv32_attr_done & bit)) {
 #define C32_ATTR(R, M, N) SPA_HIP(hipFuncSetAttribute((const void *)k_conv3x3_f32<R, M, TAPS, N>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                                       2 * M * 128 + 2 * (N + 2 * C32_HALO) * 128))
-        C32_ATTR(0, 256, 256); C32_ATTR(1, 256, 256); C32_ATTR(0, 128, 256); C32_ATTR(1, 128, 256); C32_ATTR(0, 64, 256); C32_ATTR(1, 64, 256);
-        C32_ATTR(0, 128, 128); C32_ATTR(1, 128, 128); C32_ATTR(0, 64, 128); C32_ATTR(1, 64, 128);
+        C32_ATTR(0, 256, 256); C32_ATTR(1, 256, 256); C32_ATTR(0, 128, 128); C32_ATTR(1, 128, 128); C32_ATTR(0, 64, 128); C32_ATTR(1, 64, 128);
 #undef C32_ATTR
 #define C32_ATTR(R, M, N) SPA_HIP(hipFuncSetAttribute((const void *)k_conv3x3_f32<R, M, TAPS, N, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                                       2 * M * 128 + 2 * (N + 2 * C32_HALO) * 128))
@@ -467,15 +447,14 @@ static int conv_f32_launch(spa_ctx *ctx, const float *x, int32_t B, int32_t H, i
     // (the split-plane form of the 64-channel tile is bound by its LDS reads — all eight waves read the same weight tile —
     // not by load latency: 1.77 / 1.68 / 2.25 ms with 3 / 2 / 1 workgroups per CU on the 64 -> 64 layer of 30 images)
     const int per_cu = lds > 80 * 1024 ? 1 : (lds > 53 * 1024 || (split && bm == 64) ? 2 : 3);
-    const int late = getenv("SPA_CONV32_LATE_PREFETCH") ? 1 : 0;
     long long grid = (long long)ctx->n_cu * per_cu;
     if (grid > total * zcount) grid = total * zcount;
 #define C32_LAUNCH(R, M, N)                                                                                                 \
     hipLaunchKernelGGL((k_conv3x3_f32<R, M, TAPS, N>), dim3((unsigned)grid), dim3(C32_THREADS), lds, s, x, wt, bias, residual, y,  \
-                       (const char *)zero, B, H, W, Cin, Cout, dilation, relu, xtiles, ntiles, (int)total, zcount, xz, wz, yz, late)
+                       (const char *)zero, B, H, W, Cin, Cout, dilation, relu, xtiles, ntiles, (int)total, zcount, xz, wz, yz)
 #define C32_LAUNCH_S(R, M, N)                                                                                               \
     hipLaunchKernelGGL((k_conv3x3_f32<R, M, TAPS, N, true>), dim3((unsigned)grid), dim3(C32_THREADS), lds, s, x, wt, bias, residual, y,  \
-                       (const char *)zero, B, H, W, Cin, Cout, dilation, relu, xtiles, ntiles, (int)total, zcount, xz, wz, yz, late, \
+                       (const char *)zero, B, H, W, Cin, Cout, dilation, relu, xtiles, ntiles, (int)total, zcount, xz, wz, yz, \
                        (const unsigned *)amax_in, (unsigned *)amax_out, inv_t)
     if (split) {
         // round 6: the 64- and 128-channel tiles of the 3x3 layers take the planes-in-LDS kernel of spa_convp.hip (bit-identical
@@ -491,11 +470,11 @@ static int conv_f32_launch(spa_ctx *ctx, const float *x, int32_t B, int32_t H, i
             }
             if (residual)
                 hipLaunchKernelGGL((k_conv3x3_f32<1, 64, 9, 512, true>), dim3((unsigned)grid), dim3(C32_THREADS), lds, s, x, wt, bias, residual, y,
-                                   (const char *)zero, B, H, W, Cin, Cout, dilation, relu, xtiles, ntiles, (int)total, zcount, xz, wz, yz, late,
+                                   (const char *)zero, B, H, W, Cin, Cout, dilation, relu, xtiles, ntiles, (int)total, zcount, xz, wz, yz,
                                    (const unsigned *)amax_in, (unsigned *)amax_out, inv_t);
             else
                 hipLaunchKernelGGL((k_conv3x3_f32<0, 64, 9, 512, true>), dim3((unsigned)grid), dim3(C32_THREADS), lds, s, x, wt, bias, residual, y,
-                                   (const char *)zero, B, H, W, Cin, Cout, dilation, relu, xtiles, ntiles, (int)total, zcount, xz, wz, yz, late,
+                                   (const char *)zero, B, H, W, Cin, Cout, dilation, relu, xtiles, ntiles, (int)total, zcount, xz, wz, yz,
                                    (const unsigned *)amax_in, (unsigned *)amax_out, inv_t);
             SPA_LAUNCH_CHECK();
             return SPA_OK;
@@ -517,12 +496,8 @@ static int conv_f32_launch(spa_ctx *ctx, const float *x, int32_t B, int32_t H, i
         SPA_LAUNCH_CHECK();
         return SPA_OK;
     }
-#define C32_PICK(R)                                                                     \
-    if (bm == 256) C32_LAUNCH(R, 256, 256);                                             \
-    else if (bm == 128) { if (bn == 256) C32_LAUNCH(R, 128, 256); else C32_LAUNCH(R, 128, 128); } \
-    else { if (bn == 256) C32_LAUNCH(R, 64, 256); else C32_LAUNCH(R, 64, 128); }
-    if (residual) { C32_PICK(1) } else { C32_PICK(0) }
-#undef C32_PICK
+    if (residual) { if (bm == 256) C32_LAUNCH(1, 256, 256); else if (bm == 128) C32_LAUNCH(1, 128, 128); else C32_LAUNCH(1, 64, 128); }
+    else { if (bm == 256) C32_LAUNCH(0, 256, 256); else if (bm == 128) C32_LAUNCH(0, 128, 128); else C32_LAUNCH(0, 64, 128); }
 #undef C32_LAUNCH
     SPA_LAUNCH_CHECK();
     return SPA_OK;
@@ -605,11 +580,11 @@ extern "C" int spa_conv3x3_s2_f16s(spa_ctx *ctx, const float *x, int32_t B, int3
     if (grid > total) grid = total;
     if (bm == 256)
         hipLaunchKernelGGL((k_conv3x3_f32<0, 256, 9, 128, true, 2>), dim3((unsigned)grid), dim3(C32_THREADS), lds, s, x, (const float *)wt2, bias,
-                           (const float *)nullptr, y, (const char *)zero, B, H, W, Cin, Cout, 1, relu, xtiles, ntiles, (int)total, 1, 0ll, 0ll, 0ll, 0,
+                           (const float *)nullptr, y, (const char *)zero, B, H, W, Cin, Cout, 1, relu, xtiles, ntiles, (int)total, 1, 0ll, 0ll, 0ll,
                            (const unsigned *)amax_in, (unsigned *)amax_out, inv_t, Hi, Wi, y2, csplit);
     else
         hipLaunchKernelGGL((k_conv3x3_f32<0, 128, 9, 128, true, 2>), dim3((unsigned)grid), dim3(C32_THREADS), lds, s, x, (const float *)wt2, bias,
-                           (const float *)nullptr, y, (const char *)zero, B, H, W, Cin, Cout, 1, relu, xtiles, ntiles, (int)total, 1, 0ll, 0ll, 0ll, 0,
+                           (const float *)nullptr, y, (const char *)zero, B, H, W, Cin, Cout, 1, relu, xtiles, ntiles, (int)total, 1, 0ll, 0ll, 0ll,
                            (const unsigned *)amax_in, (unsigned *)amax_out, inv_t, Hi, Wi, y2, csplit);
     SPA_LAUNCH_CHECK();
     return SPA_OK;
@@ -651,11 +626,11 @@ extern "C" int spa_conv3x3_s2_f32(spa_ctx *ctx, const float *x, int32_t B, int32
     if (grid > total) grid = total;
     if (bm == 256)
         hipLaunchKernelGGL((k_conv3x3_f32<0, 256, 9, 128, false, 2>), dim3((unsigned)grid), dim3(C32_THREADS), lds, s, x, wt, bias,
-                           (const float *)nullptr, y, (const char *)zero, B, H, W, Cin, Cout, 1, relu, xtiles, ntiles, (int)total, 1, 0ll, 0ll, 0ll, 0,
+                           (const float *)nullptr, y, (const char *)zero, B, H, W, Cin, Cout, 1, relu, xtiles, ntiles, (int)total, 1, 0ll, 0ll, 0ll,
                            (const unsigned *)nullptr, (unsigned *)nullptr, 1.f, Hi, Wi, y2, csplit);
     else
         hipLaunchKernelGGL((k_conv3x3_f32<0, 128, 9, 128, false, 2>), dim3((unsigned)grid), dim3(C32_THREADS), lds, s, x, wt, bias,
-                           (const float *)nullptr, y, (const char *)zero, B, H, W, Cin, Cout, 1, relu, xtiles, ntiles, (int)total, 1, 0ll, 0ll, 0ll, 0,
+                           (const float *)nullptr, y, (const char *)zero, B, H, W, Cin, Cout, 1, relu, xtiles, ntiles, (int)total, 1, 0ll, 0ll, 0ll,
                            (const unsigned *)nullptr, (unsigned *)nullptr, 1.f, Hi, Wi, y2, csplit);
     SPA_LAUNCH_CHECK();
     return SPA_OK;

@@ -35,7 +35,6 @@
 // fragments one fragment ahead, a quarter fragment (6 vector instructions) after every 6 matrix instructions with the order
 // pinned by scheduling barriers, changed nothing (3.53): the two waves of a SIMD already overlap each other's phases.
 #include "spa_common.h"
-#include <stdlib.h>
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -51,7 +50,7 @@ __device__ __forceinline__ void g16_lds_barrier()
 }
 
 template <int BM, int BN>
-__global__ __launch_bounds__(G16_THREADS, (BM == 256 && BN == 128) ? 3 : 2) void k_gemm_f16x3(const char *__restrict__ X, const char *__restrict__ Wt,
+__global__ __launch_bounds__(G16_THREADS, 2) void k_gemm_f16x3(const char *__restrict__ X, const char *__restrict__ Wt,
                                                             float *__restrict__ Y, int rows_per_z, int Cin, int Cout,
                                                             int ntiles, int total_tiles, int zcount, long long xz,
                                                             long long wz, long long yz, const unsigned *__restrict__ amax)
@@ -242,32 +241,17 @@ __global__ __launch_bounds__(G16_THREADS, (BM == 256 && BN == 128) ? 3 : 2) void
 // waves at the top of theirs (half a period later); each waits for its own loads (the early half counted, so that a tile's
 // stores issued behind them stay in flight) before the barrier that precedes the early half's R(q + 1).  Every accumulator
 // receives the same matrix instructions in the same order as in k_gemm_f16x3 (K steps ascending; l.h, h.l, h.h inside a
-// step): the outputs are bit-identical (tools/gemm16_ab.py compares digests across processes; tests/test_gpu_conv.py).
-// RS: row fragments split in R (1-4, the others in M; 512 -> 512 layer: 3.48 / 3.41 / 3.35 / 3.37 ms for RS = 1 / 2 / 3 / 4: default 3).  XP (diagnostic builds, tools/gemm16_stamps.py): 2 = no split (timing
-// only: the row tile read as if it held planes), 4 = no global loads (timing only), 16 = in-kernel stamps.
-template <int BM, int BN, int RS = 1, int XP = 0>
+// step): the outputs are bit-identical (tests/test_gpu_conv.py).
+template <int BM, int BN>
 __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__restrict__ X, const char *__restrict__ Wt,
                                                                  float *__restrict__ Y, int rows_per_z, int Cin, int Cout,
                                                                  int ntiles, int total_tiles, int zcount, long long xz,
-                                                                 long long wz, long long yz, const unsigned *__restrict__ amax,
-                                                                 unsigned *__restrict__ dbg = nullptr)
+                                                                 long long wz, long long yz, const unsigned *__restrict__ amax)
 {
     extern __shared__ __attribute__((aligned(1024))) char lds16[];   // [2] weight tiles | [2] row tiles, 128 bytes per row
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool late = wave >= 4;
-    // XP & 16: stamps (s_memtime, low word) of waves 0 and 4 of one workgroup over periods [Q0, Q0 + NQ), kept in LDS behind the
-    // tiles (no global store inside the loop: the counted vmcnt waits stay what they are), copied out at the end
-    constexpr int G16_Q0 = 24, G16_NQ = 40;
-    unsigned *stamps = (unsigned *)(lds16 + 2 * (BM + BN) * 128) + (wave >> 2) * (G16_NQ * 8);
-    const bool stamp_wave = (XP & 16) && blockIdx.x == 77 && (wave & 3) == 0;
-    int stamp_q = -1;
-    auto STAMP = [&](int k) {
-        if ((XP & 16) && stamp_wave && stamp_q >= 0) {
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            if (lane == 0) stamps[stamp_q * 8 + k] = (unsigned)t;
-        }
-    };
     const int all_i = zcount * total_tiles, gstep = (int)gridDim.x;
     const int nwg = total_tiles;
     float sb;
@@ -299,11 +283,11 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
     constexpr int MI = BM == 256 ? 8 : 4;
     constexpr int NJ = BN / WN / 16;
     constexpr int WROWS = MI * 16;
+    // row fragments split in R, the others in M (512 -> 512 layer: 3.48 / 3.41 / 3.35 / 3.37 ms for RS = 1 / 2 / 3 / 4)
+    constexpr int RS = 3;
     static_assert(BM / WROWS * WN == 8, "8 waves");
     static_assert(MI * NJ <= 63, "vmcnt range");
-    static_assert(RS >= 1 && RS <= NJ && MI == 8, "split schedule: 4 element pairs over 8 groups of matrix instructions");
-    constexpr bool LATE_PRESTAGE = (XP & 32) != 0;   // (XP & 32, SPA_GEMM16_LATE_PRESTAGE=1: round 6's experiment, no gain measured; off)
-    constexpr bool EARLY_STORE = (XP & 8) != 0;   // (XP & 8, SPA_GEMM16_EARLY_STORE=1: round 6's experiment below; measured 7 % slower, not the default)
+    static_assert(RS <= NJ && MI == 8, "split schedule: 4 element pairs over 8 groups of matrix instructions");
 
     char *wbuf = lds16, *xbuf = lds16 + 2 * (BM * 128);
     const int sub = lane >> 3, cs = lane & 7;
@@ -318,7 +302,6 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
         s_x = X + ((long long)zz * xz + (long long)r0 * Cin) * 4;
     };
     auto stage = [&](int t, int buf) {
-        if (XP & 4) return;
         const char *wk = s_w + (long long)t * 128;
         char *dw = wbuf + buf * (BM * 128) + wave * 1024;
 #pragma unroll
@@ -355,7 +338,7 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     g16_lds_barrier();
     if (late) g16_lds_barrier();                   // the extra barrier = half a period of delay
-    bool stored = false, pre_staged = false, late_stored = false;
+    bool stored = false;
 
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc[MI][NJ];
@@ -365,11 +348,7 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
         for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int q = 0; q < S; ++q) {
         const int buf = q & 1;
-        if (XP & 16) stamp_q = (q >= G16_Q0 && q < G16_Q0 + G16_NQ) ? q - G16_Q0 : -1;
-        STAMP(0);
-        if (!pre_staged) stage_next();             // step q + 1 (the late half stages it in front of a tile's stores: below)
-        pre_staged = false;
-        STAMP(1);
+        stage_next();                              // step q + 1
         // ---- R: the LDS reads (weight fragments, raw float32 rows) and the split of the first RS row fragments
         const char *lw = wbuf + buf * (BM * 128), *lx = xbuf + buf * (BN * 128);
         f16x8 wh[MI], wl[MI];
@@ -391,7 +370,6 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
         // elements 2e, 2e + 1 of row fragment j: the two high halves, then (a dependent pair, issued a group of matrix
         // instructions later) the two low halves
         auto split_h = [&](int j, int e) {
-            if (XP & 2) { hu[j][e] = __float_as_uint(e < 2 ? ra[j][2 * e] : rb[j][2 * e - 4]); return; }
             const float x0 = e < 2 ? ra[j][2 * e] : rb[j][2 * e - 4], x1 = e < 2 ? ra[j][2 * e + 1] : rb[j][2 * e - 3];
             unsigned h;
             asm volatile("v_fma_mixlo_f16 %0, %1, %3, 0 op_sel_hi:[0,0,0]\n\t"
@@ -400,7 +378,6 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
             hu[j][e] = h;
         };
         auto split_l = [&](int j, int e) {
-            if (XP & 2) { lu[j][e] = __float_as_uint(e < 2 ? ra[j][2 * e + 1] : rb[j][2 * e - 3]); return; }
             const float x0 = e < 2 ? ra[j][2 * e] : rb[j][2 * e - 4], x1 = e < 2 ? ra[j][2 * e + 1] : rb[j][2 * e - 3];
             unsigned l;
             asm volatile("v_fma_mixlo_f16 %0, %1, %3, -%4 op_sel_hi:[0,0,1]\n\t"
@@ -412,29 +389,14 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
         for (int j = 0; j < RS; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) { split_h(j, e); split_l(j, e); }
-        STAMP(2);
-        // the late half's share of step q + 1 must have landed before the early half reads it behind this barrier.  Round 6 experiment
-        // (LATE_PRESTAGE): a tile's 256 KB of stores per workgroup take ~10 k cycles to drain and this `vmcnt(0)` half a period behind
-        // them holds the workgroup (stamps: periods of 15-25 k cycles at a tile's end against 4.3 k); with the late half staging this
-        // share IN FRONT of its stores the wait can leave them in flight — measured: no gain (1.04 against 1.05 PFLOP/s): the stall only
-        // moves to the next wait, a CU's memory pipe (1 MB of loads + 256 KB of stores per tile, ~18 B / cycle) is what the tile waits for
-        if (late) {
-            if (late_stored) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MI * NJ) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        late_stored = false;
-        STAMP(3);
+        // the late half's share of step q + 1 must have landed before the early half reads it behind this barrier (a tile's
+        // stores drain in front of this wait; staging this share in front of them instead was measured no faster: DESIGN.md)
+        if (late) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         g16_lds_barrier();
-        STAMP(4);
         // ---- M: row fragment by row fragment, small terms first (they meet the accumulator while it is small); the split of
-        // fragment j + RS rides between the matrix instructions of fragment j.
-        // Round 6 experiment (EARLY_STORE): in-kernel stamps put the burst of 32 stores per wave behind a tile's last K step (every wave
-        // of the workgroup within half a period of each other) at ~16 % of the kernel — periods that end a tile take 15-25 k cycles
-        // against a median of 4.3 k (3 072 of them matrix work).  Storing (and clearing) every accumulator one accumulator behind its
-        // final matrix instruction instead, between the matrix instructions of the last step, was measured 7 % SLOWER (1.07 -> 1.00
-        // PFLOP/s executed, same bits): a store between matrix instructions waits for its accumulator and breaks the matrix stream
-        // the way an LDS-DMA instruction does.  The burst stays.
-        const bool last_step = c_t + 1 == nk;
+        // fragment j + RS rides between the matrix instructions of fragment j.  (Storing each accumulator between the matrix
+        // instructions of a tile's last step was measured 7 % slower: a store waits for its accumulator and breaks the matrix
+        // stream.  The tile's stores go out as one burst after the step.)
         float *const e_y = Y + (long long)c_z * yz + ((long long)c_r0 + wn * (NJ * 16) + (lane & 15)) * Cout + (c_n0 + wm * WROWS + (lane >> 4) * 4);
         auto store_acc = [&](int i, int j) {
             *(float4 *)(e_y + (long long)(j * 16) * Cout + i * 16) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
@@ -449,26 +411,15 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], plj, acc[i][j], 0, 0, 0);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], phj, acc[i][j], 0, 0, 0);
                 if (j + RS < NJ) { if ((i & 1) == 0) split_h(j + RS, i >> 1); else split_l(j + RS, i >> 1); }
-                if (EARLY_STORE && last_step && (i > 0 || j > 0)) { if (i > 0) store_acc(i - 1, j); else store_acc(MI - 1, j - 1); }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        STAMP(5);
         if (++c_t == nk) {
             // ---- a tile is complete: lane holds channels c..c+3 (c = tile channel base + (lane>>4)*4) of row (lane & 15)
-            if (late && LATE_PRESTAGE) {
-                // (the buffer of step q + 2 = the buffer of step q, which both halves finished reading before this period's mid barrier)
-                stage_next();
-                pre_staged = true;
-                late_stored = true;
-            }
-            if (EARLY_STORE) store_acc(MI - 1, NJ - 1);
-            else {
 #pragma unroll
-                for (int j = 0; j < NJ; ++j)
+            for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                    for (int i = 0; i < MI; ++i) store_acc(i, j);
-            }
+                for (int i = 0; i < MI; ++i) store_acc(i, j);
             stored = true;
             c_t = 0; c_vid += gstep;
             if (c_vid < all_i) {
@@ -483,218 +434,11 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
             // the early half's share of step q + 1 (staged at the top of this period): a tile's stores issued after it may stay in flight
             if (stored) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MI * NJ) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            STAMP(6);
             g16_lds_barrier();
         } else if (q + 1 < S) {
-            STAMP(6);
             g16_lds_barrier();
         }
         stored = false;
-        STAMP(7);
-    }
-    if ((XP & 16) && stamp_wave && dbg) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int i = lane; i < G16_NQ * 8; i += 64) dbg[(wave >> 2) * (G16_NQ * 8) + i] = stamps[i];
-    }
-}
-
-// Round 6: the PIPELINED form.  One barrier per K step and nothing in front of the matrix instructions: while step q multiplies out
-// of registers, the same wave reads step q's weight fragments one channel block ahead (i-outer order: a block's two fragments die
-// after its 12 matrix instructions), reads the raw float32 rows of step q + 1 and splits them into the planes of step q + 1 (a row
-// fragment at a time: 8 transient registers), and stages weights(q + 1) and rows(q + 2) by LDS-DMA — all between matrix instructions,
-// order pinned by scheduling barriers.  Buffers: two weight tiles (weights(q) are read during step q, weights(q + 1) land meanwhile)
-// and two row tiles (rows(q + 1) are read during step q, rows(q + 2) land meanwhile in the buffer rows(q) left during step q - 1):
-// the same 128 KB.  Registers: accumulators 128, planes of steps q and q + 1 32 + 32, weight fragments 8 + 8, raw rows 8.
-// Every accumulator still receives l.h, h.l, h.h of K step after K step in ascending order: the same bits as k_gemm_f16x3(_stag).
-template <int BM, int BN>
-__global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_pipe(const char *__restrict__ X, const char *__restrict__ Wt,
-                                                                 float *__restrict__ Y, int rows_per_z, int Cin, int Cout,
-                                                                 int ntiles, int total_tiles, int zcount, long long xz,
-                                                                 long long wz, long long yz, const unsigned *__restrict__ amax)
-{
-    static_assert(BM == 256 && BN == 256, "one shape");
-    extern __shared__ __attribute__((aligned(1024))) char lds16[];   // [2] weight tiles | [2] row tiles, 128 bytes per row
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int all_i = zcount * total_tiles, gstep = (int)gridDim.x;
-    const int nwg = total_tiles;
-    float sb;
-    {
-        const unsigned bits = *amax;
-        int e = (int)(bits >> 23) - 127;
-        e = e < -100 ? -100 : (e > 100 ? 100 : e);
-        sb = __uint_as_float((unsigned)(127 + 14 - (bits == 0u ? 0 : e)) << 23);
-    }
-    struct Pos { int r0, n0, zz; float zscale; };
-    auto locate = [&](int vid) {
-        Pos p;
-        const int z = vid / total_tiles;
-        const int zi = z / 6, zj = z - zi * 6;
-        const int psum = ((0x433444 >> (4 * zi)) & 15) + ((0x433444 >> (4 * zj)) & 15);
-        int id = vid - z * total_tiles;
-        {
-            const int q = nwg / 8, rem = nwg % 8, xcd = id % 8, idx = id / 8;
-            id = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + idx;
-        }
-        const int nt = id % ntiles, pt = id / ntiles;
-        p.zz = __builtin_amdgcn_readfirstlane(z);
-        p.r0 = __builtin_amdgcn_readfirstlane(pt * BN);
-        p.n0 = __builtin_amdgcn_readfirstlane(nt * BM);
-        p.zscale = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sb * __uint_as_float((unsigned)(127 - psum) << 23))));
-        return p;
-    };
-    constexpr int WN = 4, MI = 8, NJ = 4, WROWS = MI * 16;
-    char *const wbuf = lds16, *const xbuf = lds16 + 2 * (BM * 128);
-    const int sub = lane >> 3, cs = lane & 7;
-    const int chunk_byte = (cs ^ sub) << 4;
-    const int nk = Cin / 32;
-    const unsigned lane_off = (unsigned)((wave * 8 + sub) * Cin * 4 + chunk_byte);
-    if ((int)blockIdx.x >= all_i) return;
-    const int my_tiles = (all_i - (int)blockIdx.x + gstep - 1) / gstep;
-    const int S = my_tiles * nk;                                    // K steps of this workgroup
-
-    // cursors: the tile of the step being multiplied (cur), its successor (nxt); the weight stage cursor is one step ahead of the
-    // multiplying one, the row stage cursor two, the split cursor one: each only ever sits in cur or nxt (nk >= 2)
-    Pos cur = locate((int)blockIdx.x), nxt = cur;
-    int nxt_vid = (int)blockIdx.x + gstep;
-    if (nxt_vid < all_i) nxt = locate(nxt_vid);
-    int c_t = 0;
-    auto at = [&](int ahead, int &t_out) -> const Pos & {
-        const int t = c_t + ahead;
-        if (t < nk) { t_out = t; return cur; }
-        t_out = t - nk;
-        return nxt;
-    };
-    auto stage_w = [&](int ahead, int buf) {
-        int t;
-        const Pos &p = at(ahead, t);
-        const char *wk = Wt + ((long long)p.zz * wz + (long long)p.n0 * Cin) * 4 + (long long)t * 128;
-        char *dw = wbuf + buf * (BM * 128) + wave * 1024;
-#pragma unroll
-        for (int r = 0; r < BM / 64; ++r)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wk + (long long)r * 64 * Cin * 4 + lane_off),
-                                             (__attribute__((address_space(3))) void *)(dw + r * 8192), 16, 0, 0);
-    };
-    auto stage_x = [&](int ahead, int buf) {
-        int t;
-        const Pos &p = at(ahead, t);
-        const char *xk = X + ((long long)p.zz * xz + (long long)p.r0 * Cin) * 4 + (long long)t * 128;
-        char *dx = xbuf + buf * (BN * 128) + wave * 1024;
-#pragma unroll
-        for (int r = 0; r < BN / 64; ++r)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(xk + (long long)r * 64 * Cin * 4 + lane_off),
-                                             (__attribute__((address_space(3))) void *)(dx + r * 8192), 16, 0, 0);
-    };
-    const int wm = wave / WN, wn = wave % WN;
-    const int frow = lane & 15, fk = lane >> 4;
-    const int w_h = (wm * WROWS + frow) * 128 + ((fk ^ (frow & 7)) << 4), w_l = (wm * WROWS + frow) * 128 + (((4 + fk) ^ (frow & 7)) << 4);
-    const int x_a = (wn * (NJ * 16) + frow) * 128 + (((2 * fk) ^ (frow & 7)) << 4), x_b = (wn * (NJ * 16) + frow) * 128 + (((2 * fk + 1) ^ (frow & 7)) << 4);
-
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    auto split_pair = [&](float x0, float x1, float sc, unsigned &l) {
-        unsigned h, lo;
-        asm("v_fma_mixlo_f16 %0, %2, %4, 0 op_sel_hi:[0,0,0]\n\t"
-            "v_fma_mixhi_f16 %0, %3, %4, 0 op_sel_hi:[0,0,0]\n\t"
-            "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-            "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-            : "=&v"(h), "=&v"(lo) : "v"(x0), "v"(x1), "s"(sc));
-        l = lo;
-        return h;
-    };
-
-    // ---- prologue: weights(0), rows(0), rows(1); the planes of step 0
-    stage_w(0, 0);
-    stage_x(0, 0);
-    if (S > 1) stage_x(1, 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    g16_lds_barrier();
-    u32x4 hu[NJ], lu[NJ], hn[NJ], ln[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const f32x4 a = *(const f32x4 *)(xbuf + j * 2048 + x_a), b = *(const f32x4 *)(xbuf + j * 2048 + x_b);
-        unsigned l;
-        hu[j][0] = split_pair(a[0], a[1], cur.zscale, l); lu[j][0] = l;
-        hu[j][1] = split_pair(a[2], a[3], cur.zscale, l); lu[j][1] = l;
-        hu[j][2] = split_pair(b[0], b[1], cur.zscale, l); lu[j][2] = l;
-        hu[j][3] = split_pair(b[2], b[3], cur.zscale, l); lu[j][3] = l;
-    }
-    f32x4 acc[MI][NJ];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    // (two steps per loop iteration with the two plane sets swapping roles: no register copies between steps)
-    auto kstep = [&](int q, u32x4 (&hu)[NJ], u32x4 (&lu)[NJ], u32x4 (&hn)[NJ], u32x4 (&ln)[NJ]) {
-        const bool s1 = q + 1 < S, s2 = q + 2 < S;
-        const char *lw = wbuf + (q & 1) * (BM * 128);
-        const char *lxn = xbuf + ((q + 1) & 1) * (BN * 128);              // rows of step q + 1
-        int tn;
-        const float scn = at(1, tn).zscale;                              // their scale
-        f16x8 wh0, wl0, wh1, wl1;                                          // weight fragments of channel blocks i (even: 0, odd: 1)
-        wh0 = *(const f16x8 *)(lw + w_h);
-        wl0 = *(const f16x8 *)(lw + w_l);
-        f32x4 ra, rb;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-            // next block's weight fragments
-            if (i + 1 < MI) {
-                if (i & 1) { wh0 = *(const f16x8 *)(lw + (i + 1) * 2048 + w_h); wl0 = *(const f16x8 *)(lw + (i + 1) * 2048 + w_l); }
-                else { wh1 = *(const f16x8 *)(lw + (i + 1) * 2048 + w_h); wl1 = *(const f16x8 *)(lw + (i + 1) * 2048 + w_l); }
-            }
-            // rows of step q + 1: fragment j = i / 2 is read at even i and split behind the matrix instructions of blocks i, i + 1
-            if (s1 && (i & 1) == 0) { ra = *(const f32x4 *)(lxn + (i >> 1) * 2048 + x_a); rb = *(const f32x4 *)(lxn + (i >> 1) * 2048 + x_b); }
-            const f16x8 wh = (i & 1) ? wh1 : wh0, wl = (i & 1) ? wl1 : wl0;
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const f16x8 phj = __builtin_bit_cast(f16x8, hu[j]), plj = __builtin_bit_cast(f16x8, lu[j]);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, phj, acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, plj, acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, phj, acc[i][j], 0, 0, 0);
-                if (s1 && j >= 2) {
-                    // element pair e of row fragment jn = i / 2: pairs 0, 1 behind block i even, 2, 3 behind block i odd
-                    const int jn = i >> 1, e = 2 * (i & 1) + (j - 2);
-                    const float x0 = e < 2 ? ra[2 * e] : rb[2 * e - 4], x1 = e < 2 ? ra[2 * e + 1] : rb[2 * e - 3];
-                    unsigned l;
-                    hn[jn][e] = split_pair(x0, x1, scn, l);
-                    ln[jn][e] = l;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // staging: weights of step q + 1 into the other weight tile, rows of step q + 2 into the tile rows(q) left a step ago
-            if (i == 0) { if (s1) stage_w(1, (q + 1) & 1); __builtin_amdgcn_sched_barrier(0); }
-            if (i == 1) { if (s2) stage_x(2, q & 1); __builtin_amdgcn_sched_barrier(0); }
-        }
-        bool stored = false;
-        if (c_t == nk - 1) {
-            // ---- a tile is complete: lane holds channels c..c+3 (c = tile channel base + (lane>>4)*4) of row (lane & 15)
-            float *e_y = Y + (long long)cur.zz * yz;
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const long long row = (long long)cur.r0 + wn * (NJ * 16) + j * 16 + (lane & 15);
-#pragma unroll
-                for (int i = 0; i < MI; ++i) {
-                    const int c = cur.n0 + wm * WROWS + i * 16 + (lane >> 4) * 4;
-                    *(float4 *)(e_y + row * Cout + c) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-                    acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                }
-            }
-            stored = true;
-            c_t = 0;
-            cur = nxt;
-            nxt_vid += gstep;
-            if (nxt_vid < all_i) nxt = locate(nxt_vid);
-        } else ++c_t;
-        if (s1) {
-            // what this step staged has landed (a tile's stores, issued behind it, stay in flight); every wave has read the buffers of step q
-            if (stored) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MI * NJ) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            g16_lds_barrier();
-        }
-    };
-    for (int q = 0; q < S; q += 2) {
-        kstep(q, hu, lu, hn, ln);
-        if (q + 1 < S) kstep(q + 1, hn, ln, hu, lu);
     }
 }
 
@@ -708,93 +452,31 @@ int gemm_f16x3_raw(spa_ctx *ctx, const float *x, long long rows, int32_t Cin, co
     SPA_ARG(Cin % 32 == 0 && Cout % 128 == 0);
     SPA_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)wt % 16) == 0 && ((uintptr_t)y % 16) == 0);
     hipStream_t s = spa_stream(stream);
-    static const int force_tile = getenv("SPA_GEMM16_TILE") ? atoi(getenv("SPA_GEMM16_TILE")) : 0;      // experiments: 128
-    const int bm = (Cout % 256 == 0 && force_tile != 128) ? 256 : 128;
-    // (SPA_GEMM16_TILE=2128, round 6 experiment: 256 channels x 128 rows, two LDS stages of 48 KB, <= 168 registers per wave —
-    // room for a third wave per SIMD from another kernel, tools/coresidency_probe.py)
-    const int bn = (bm == 256 && force_tile != 2128) ? 256 : 128;
+    const int bm = Cout % 256 == 0 ? 256 : 128, bn = bm;
     const int ntiles = Cout / bm;
     const long long total = rows / bn * ntiles;
     SPA_ARG(total < (1ll << 31));
     const size_t lds = 2 * (size_t)(bm + bn) * 128;
-    if (!(ctx->gemm16_attr_done & 1)) {
-        SPA_HIP(hipFuncSetAttribute((const void *)k_gemm_f16x3<256, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
-        SPA_HIP(hipFuncSetAttribute((const void *)k_gemm_f16x3<128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * 128));
-        SPA_HIP(hipFuncSetAttribute((const void *)k_gemm_f16x3<256, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 384 * 128));
-        ctx->gemm16_attr_done |= 1;
-    }
     SpaProfScope prof_(ctx, bm == 256 ? PROF_DRN_GEMM16 : PROF_DRN_GEMM16_N, s);
-    static const int force_per_cu = getenv("SPA_GEMM16_PER_CU") ? atoi(getenv("SPA_GEMM16_PER_CU")) : 0;
-    const int per_cu = force_per_cu > 0 ? force_per_cu : (lds > 80 * 1024 ? 1 : 2);
+    const int per_cu = lds > 80 * 1024 ? 1 : 2;
     long long grid = (long long)ctx->n_cu * per_cu;
     if (grid > total * zcount) grid = total * zcount;
-    // SPA_GEMM16_STAGGER (read once): unset = the staggered kernel with three of the four row fragments split in R (the default for the 256 x 256
-    // tile); 0 = k_gemm_f16x3 (round 3's kernel: kept for A/B runs and for the 128 x 128 tile); 1-4 = row fragments split in R;
-    // diagnostic builds of the RS = 1 form (timing only unless stamps alone): + 8 no split, + 16 no global loads, + 32 in-kernel
-    // stamps (tools/gemm16_stamps.py; RS = 1 or 2)
-    static const int stagger = getenv("SPA_GEMM16_STAGGER") ? atoi(getenv("SPA_GEMM16_STAGGER")) : 3;
-    static const int pipe = getenv("SPA_GEMM16_PIPE") ? atoi(getenv("SPA_GEMM16_PIPE")) : 0;
-    if (pipe && bm == 256 && bn == 256 && Cin >= 64) {
-        if (!(ctx->gemm16_attr_done & 2)) {
-            SPA_HIP(hipFuncSetAttribute((const void *)k_gemm_f16x3_pipe<256, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
-            ctx->gemm16_attr_done |= 2;
-        }
-        hipLaunchKernelGGL((k_gemm_f16x3_pipe<256, 256>), dim3((unsigned)grid), dim3(G16_THREADS), lds, s, (const char *)x, (const char *)wt, y,
-                           (int)rows, Cin, Cout, ntiles, (int)total, zcount, rows * Cin, (long long)Cout * Cin, rows * Cout, (const unsigned *)amax);
-        SPA_LAUNCH_CHECK();
-        return SPA_OK;
-    }
-    if (bm == 256 && bn == 128) {
-        hipLaunchKernelGGL((k_gemm_f16x3<256, 128>), dim3((unsigned)grid), dim3(G16_THREADS), lds, s, (const char *)x, (const char *)wt, y,
-                           (int)rows, Cin, Cout, ntiles, (int)total, zcount, rows * Cin, (long long)Cout * Cin, rows * Cout, (const unsigned *)amax);
-        SPA_LAUNCH_CHECK();
-        return SPA_OK;
-    }
-    if (stagger && bm == 256) {
+    // the 256 x 256 tile: the staggered kernel; the 128 x 128 tile (128 output channels): k_gemm_f16x3
+    if (bm == 256) {
         if (!ctx->gemm16s_attr_done) {
-#define G16S_ATTR(RS, XP) SPA_HIP(hipFuncSetAttribute((const void *)k_gemm_f16x3_stag<256, 256, RS, XP>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128 + ((XP) & 16 ? 4096 : 0)))
-            G16S_ATTR(1, 0); G16S_ATTR(2, 0); G16S_ATTR(3, 0); G16S_ATTR(4, 0); G16S_ATTR(3, 8); G16S_ATTR(3, 32);
-#ifdef SPA_DIAG
-            G16S_ATTR(1, 2); G16S_ATTR(1, 4); G16S_ATTR(1, 6); G16S_ATTR(1, 16); G16S_ATTR(2, 16); G16S_ATTR(1, 18); G16S_ATTR(1, 20);
-#endif
-#undef G16S_ATTR
+            SPA_HIP(hipFuncSetAttribute((const void *)k_gemm_f16x3_stag<256, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
             ctx->gemm16s_attr_done = 1;
         }
-        unsigned *dbg = nullptr;
-        if (stagger & 32) {
-            int rc = spa_ws_reserve(ctx, WS_DEBUG, 4096, (void **)&dbg);
-            if (rc != SPA_OK) return rc;
-        }
-#define G16S_LAUNCH(RS, XP) hipLaunchKernelGGL((k_gemm_f16x3_stag<256, 256, RS, XP>), dim3((unsigned)grid), dim3(G16_THREADS), lds + ((XP) & 16 ? 4096 : 0), s, (const char *)x, (const char *)wt, y, \
-                               (int)rows, Cin, Cout, ntiles, (int)total, zcount, rows * Cin, (long long)Cout * Cin, rows * Cout, (const unsigned *)amax, dbg)
-        const int rs = stagger & 7, diag = stagger >> 3;          // diag: 1 no split, 2 no loads, 4 stamps
-        static const int early_store = getenv("SPA_GEMM16_EARLY_STORE") ? atoi(getenv("SPA_GEMM16_EARLY_STORE")) : 0;
-        static const int late_prestage = getenv("SPA_GEMM16_LATE_PRESTAGE") ? atoi(getenv("SPA_GEMM16_LATE_PRESTAGE")) : 0;
-        if (diag == 0 && early_store) G16S_LAUNCH(3, 8);
-        else if (diag == 0 && late_prestage) G16S_LAUNCH(3, 32);
-        else if (diag == 0) { if (rs == 1) G16S_LAUNCH(1, 0); else if (rs == 2) G16S_LAUNCH(2, 0); else if (rs == 4) G16S_LAUNCH(4, 0); else G16S_LAUNCH(3, 0); }
-#ifdef SPA_DIAG
-        // timing-only forms (no split / no global loads: WRONG numbers) and the in-kernel stamps exist in diagnostic builds only
-        // (make EXTRA=-DSPA_DIAG): a stray SPA_GEMM16_STAGGER cannot select them in the production library
-        else if (diag == 1) G16S_LAUNCH(1, 2);
-        else if (diag == 2) G16S_LAUNCH(1, 4);
-        else if (diag == 3) G16S_LAUNCH(1, 6);
-        else if (diag == 4) { if (rs == 2) G16S_LAUNCH(2, 16); else G16S_LAUNCH(1, 16); }
-        else if (diag == 5) G16S_LAUNCH(1, 18);
-        else G16S_LAUNCH(1, 20);
-#else
-        else SPA_ARG(!"SPA_GEMM16_STAGGER >= 8 selects a diagnostic form of the GEMM: build libspalign with EXTRA=-DSPA_DIAG");
-#endif
-#undef G16S_LAUNCH
-        SPA_LAUNCH_CHECK();
-        return SPA_OK;
-    }
-    if (bm == 256)
-        hipLaunchKernelGGL((k_gemm_f16x3<256, 256>), dim3((unsigned)grid), dim3(G16_THREADS), lds, s, (const char *)x, (const char *)wt, y,
+        hipLaunchKernelGGL((k_gemm_f16x3_stag<256, 256>), dim3((unsigned)grid), dim3(G16_THREADS), lds, s, (const char *)x, (const char *)wt, y,
                            (int)rows, Cin, Cout, ntiles, (int)total, zcount, rows * Cin, (long long)Cout * Cin, rows * Cout, (const unsigned *)amax);
-    else
+    } else {
+        if (!ctx->gemm16_attr_done) {
+            SPA_HIP(hipFuncSetAttribute((const void *)k_gemm_f16x3<128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * 128));
+            ctx->gemm16_attr_done = 1;
+        }
         hipLaunchKernelGGL((k_gemm_f16x3<128, 128>), dim3((unsigned)grid), dim3(G16_THREADS), lds, s, (const char *)x, (const char *)wt, y,
                            (int)rows, Cin, Cout, ntiles, (int)total, zcount, rows * Cin, (long long)Cout * Cin, rows * Cout, (const unsigned *)amax);
+    }
     SPA_LAUNCH_CHECK();
     return SPA_OK;
 }

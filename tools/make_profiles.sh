@@ -32,7 +32,6 @@ v drn_c_26_bf16 --arch drn_c_26 --dtype bf16
 v reference_operating_point --superpixel_method felzenszwalb --height 224 --width 224 --arch drn_c_26 --pool_mode anchor --n_clusters 4
 v k4 --n_clusters 4
 SPA_KM_HOST_INIT=1 python3 bench.py --no_cpu_baseline --no_exact_fp32 --steps 20 --warmup 5 --n_clusters 4 2> gpurun_out/final_variant_k4_host_init.err | tail -1 > gpurun_out/final_variant_k4_host_init.json
-SPA_GEMM16_STAGGER=0 SPA_CONV16_STAGGER=0 python3 bench.py --no_cpu_baseline --no_exact_fp32 --steps 20 --warmup 5 2> gpurun_out/final_variant_round4_kernels.err | tail -1 > gpurun_out/final_variant_round4_kernels.json
 python3 tools/h2h_probe2.py --steps 10 2>&1 | grep -E "device resident|host loop" > gpurun_out/final_h2h_probe.txt
 SPA_LATE_DOWNLOAD=0 python3 tools/h2h_probe2.py --steps 10 2>&1 | grep -E "device resident|host loop" | sed "s/^/[downloads enqueued at once, behind an event] /" >> gpurun_out/final_h2h_probe.txt
 python3 -m pytest tests/test_gpu_hostile.py tests/test_gpu_descriptor_parity.py -q -s 2>&1 | grep -E "hostile|per-channel|bulk error|descriptors|passed|failed" > gpurun_out/final_hostile.txt
