@@ -17,16 +17,25 @@ Prints ONE JSON line on rank 0 (see README/DESIGN for the fields).  `value` / `m
 8d's region — the reference's own step (batch_spalign_kmeans.py:427-458: H->D at :431, D->H at :355-357):
 batches of decoded 8-bit images in pinned host memory -> cluster + road masks in pinned host memory
 through pipeline.HostStream (uploads and downloads double buffered on copy streams under the kernels).
-`device_resident_value` / `device_resident_ms_per_step` time the same K steps with the batches already in
-HBM (a loop of its own, run first).  Both loops run the pipeline as the drivers do (LabelPipeline's default): the superpixel
-branch on a second stream beside the front of the DRN forward; `--one_stream` puts every kernel on its own.  `kernels` holds one roofline-shaped entry per hand-written kernel
+`kernels` holds one roofline-shaped entry per hand-written kernel
 family of libspalign (HIP events on the launch stream, recorded during the headline loop): HBM-bound ones against 8 TB/s
 with their algorithmic bytes, the float32-MFMA stem against the fp32 matrix peak; `roofline` is the
 family with the most time per step, whichever it is.  `drn` reports the matrix side of the step (libspalign's own
-convolutions; none is MIOpen's in the float32 forward).  `cpu_baseline` times, on the host cores, the C
+convolutions; none is MIOpen's in the float32 forward).
+
+A plain run does only what that line needs: it sets up, warms up, times the headline loop, writes --dump-outputs and
+prints the line.  `--full` adds the measurements that take runs of their own, in this order after the warm-up:
+`device_resident_value` / `device_resident_ms_per_step` time the same K steps with the batches already in
+HBM (a loop of its own, run before the headline loop; with --no_host_loop it is the headline loop and always runs);
+`exact_fp32_value` times the headline region again on float32 matrix instructions (--no_exact_fp32 skips it);
+`cpu_baseline` times, on the host cores, the C
 restatement (oracle, single thread and all cores with images sharded over threads), the same DRN
 through PyTorch-CPU and BASELINE.json's named comparator (NumPy pooling + scipy.cluster.vq.kmeans2)
-on a bounded sample, rank 0 at N = 1 only.
+on a bounded sample, rank 0 at N = 1 only (--no_cpu_baseline skips it).  Without --full those fields are None or absent.
+(Anchor pooling and k > 2 draw from the reference's random streams batch after batch, so there the device-resident loop of
+--full moves the headline loop's draws along; mean pooling with k = 2, the default, draws nothing.)
+Every loop runs the pipeline as the drivers do (LabelPipeline's default): the superpixel
+branch on a second stream beside the front of the DRN forward; `--one_stream` puts every kernel on its own.
 
 `--dump-outputs DIR` writes what the headline loop returned for its last batch (rank 0: masks, superpixels,
 descriptors, prior, assignment, feature map) as DIR/<name>.npy in float32 / float64, large arrays as a fixed seeded
@@ -77,8 +86,12 @@ def parse():
                    help='parts of the batch run on side streams inside the DRN forward (epilogue passes of one part '
                         'under the convolutions of the other): 2 shortens the forward by 2 %% but the label kernels '
                         'that follow run slower by as much (measured), so the default is 1')
-    p.add_argument('--no_cpu_baseline', action='store_true')
-    p.add_argument('--no_exact_fp32', action='store_true', help='skip the extra K steps on float32 matrix instructions (`exact_fp32_value`)')
+    p.add_argument('--full', action='store_true',
+                   help='also run what the headline figure does not need: the device-resident loop, the float32-matrix-instruction '
+                        'loop and the CPU baseline (see the module docstring)')
+    p.add_argument('--no_cpu_baseline', action='store_true', help='--full: skip the CPU baseline (`cpu_baseline`)')
+    p.add_argument('--no_exact_fp32', action='store_true',
+                   help='--full: skip the extra K steps on float32 matrix instructions (`exact_fp32_value`)')
     p.add_argument('--cpu_sample', type=int, default=1, help='images of the PyTorch-CPU DRN sample')
     p.add_argument('--cpu_threads', type=int, default=64,
                    help='threads (= images in flight) of the all-cores oracle row: min(host cores, this)')
@@ -393,11 +406,16 @@ def main():
     # distinct batches in pinned host memory (the host loop's source) and their device copies.  Default: 8-bit-valued
     # images, held on the host as a PNG decoder leaves them — (B,H,W,3) uint8 — like the drivers of cli.py hold them
     integer = not a.float_images
+    pins = [torch.empty((B, 3, H, W), dtype=torch.float32).pin_memory() for _ in range(NB)]
+    # the batches are generated side by side on host threads (numpy drops the GIL in its array loops); each batch has its
+    # own seeds and output, so the images are those of one batch after the other
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(min(NB, 8)) as ex:
+        gt_np = list(ex.map(lambda nb: make_batch(spa.synth, B, H, W, scene=(a.superpixel_method == 'felzenszwalb'),
+                                                  seed0=1000 * rank + 4 * nb, out=pins[nb].numpy(), integer=integer)[1],
+                            range(NB)))
     host, gts, dev = [], [], []
-    for nb in range(NB):
-        pin = torch.empty((B, 3, H, W), dtype=torch.float32).pin_memory()
-        _, g = make_batch(spa.synth, B, H, W, scene=(a.superpixel_method == 'felzenszwalb'),
-                          seed0=1000 * rank + 4 * nb, out=pin.numpy(), integer=integer)
+    for pin, g in zip(pins, gt_np):
         dev.append(pin.cuda())
         if integer:
             u8 = torch.empty((B, H, W, 3), dtype=torch.uint8).pin_memory()
@@ -405,6 +423,7 @@ def main():
             pin = u8
         host.append(pin)
         gts.append(torch.from_numpy(g).cuda())
+    del pins, gt_np
     conf_total = torch.zeros((B, 4), dtype=torch.int64, device='cuda')
     cur = [0]
 
@@ -510,7 +529,7 @@ def main():
         assert n_out == B * a.steps
         return dt, res, evs, g
 
-    # the device-resident loop first (plain), then the headline loop with the per-kernel events
+    # the device-resident loop first (--full; with --no_host_loop it is the headline), then the headline loop with the per-kernel events
     host_headline = not a.no_host_loop
     conf_total.zero_()
     for key in COUNTERS:
@@ -518,7 +537,9 @@ def main():
     drn._EPILOGUE['c16'] = {}
     if not host_headline and not a.no_prof:
         eng.prof_enable(True)
-    dt_dev, res, evs, g = loop_device(headline=not host_headline)
+    dt_dev = None
+    if a.full or not host_headline:
+        dt_dev, res, evs, g = loop_device(headline=not host_headline)
     dt_h = None
     if host_headline:
         dt_h, res, evs, g = loop_host(headline=True)
@@ -576,7 +597,7 @@ def main():
     # chains) instead of two half-precision planes per operand: `exact_fp32_value` (VERDICT r4, next #2 / missing #3), the
     # same region as `value`, K steps after two warm-up steps, counters and events of the headline loop untouched
     exact_fp32 = None
-    if a.dtype == 'fp32' and drn._EPILOGUE['split_gemm'] and not a.no_exact_fp32:
+    if a.full and a.dtype == 'fp32' and drn._EPILOGUE['split_gemm'] and not a.no_exact_fp32:
         saved_counters = {k: drn._EPILOGUE[k] for k in COUNTERS}
         drn._EPILOGUE['split_gemm'] = False
         try:
@@ -729,7 +750,7 @@ def main():
                   else 'images/sec superpixel-align labelling (%dx%d)' % (H, W),
         'value': round(total_images / dt, 3), 'unit': 'images/sec', 'n_gpus': ws, 'steps': a.steps,
         'warmup': a.warmup, 'ms_per_step': round(dt / a.steps * 1e3, 3), 'higher_is_better': True,
-        'scaling': 'weak', 'vs_baseline': None,
+        'scaling': 'weak', 'vs_baseline': None, 'full': a.full,
         'dtype': ('f32 as 2 x f16 planes, f32 accumulate' if split16 else 'f32') if a.dtype == 'fp32' else 'bf16',
         'data': 'synthetic',
         'timed_region': ('host to host (SURVEY.md 8d; reference batch_spalign_kmeans.py:427-458): decoded batches in pinned host '
@@ -741,8 +762,8 @@ def main():
                             'reference\'s arithmetic (cuDNN float32, models/drn.py:304-325); `value` multiplies two half-precision planes per '
                             'operand instead — pooled descriptors within 1e-4 relative of this path, label maps identical '
                             '(tests/test_gpu_descriptor_parity.py)') if exact_fp32 else None,
-        'device_resident_value': round(total_images / dt_dev, 3),
-        'device_resident_ms_per_step': round(dt_dev / a.steps * 1e3, 3),
+        'device_resident_value': round(total_images / dt_dev, 3) if dt_dev is not None else None,
+        'device_resident_ms_per_step': round(dt_dev / a.steps * 1e3, 3) if dt_dev is not None else None,
         'config': {'workload': 'BASELINE configs[1] x batch: %s %s features + HIP %s/%s-pool/'
                                'prior/k-means(k=%d)/paint, %dx%d, %d images per step per GPU, '
                                '%d distinct batches rotating, %s images, random-init weights'
@@ -796,7 +817,7 @@ def main():
         'dumped_outputs': {'dir': a.dump_outputs, 'arrays': dumped, 'sample_cap': DUMP_CAP, 'sample_seed': DUMP_SEED}
                           if dumped is not None else None,
     }
-    if ws == 1 and not a.no_cpu_baseline:
+    if ws == 1 and a.full and not a.no_cpu_baseline:
         try:
             out['cpu_baseline'] = cpu_baseline(a, spa.synth, a.cpu_sample)
         except Exception as exc:                      # the baseline must never hide the GPU number

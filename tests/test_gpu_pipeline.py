@@ -369,7 +369,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
            '--master-addr', '127.0.0.1', '--master-port', '29611', os.path.join(ROOT, 'bench.py'),
            '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2', '--height', '128', '--width', '256',
-           '--n_slic_segments', '40', '--drn_sub_batch', '2', '--no_cpu_baseline']
+           '--n_slic_segments', '40', '--drn_sub_batch', '2', '--full', '--no_cpu_baseline']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -388,6 +388,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     assert len(m['per_rank_images_per_sec']) == 2 and all(v > 0 for v in m['per_rank_images_per_sec'])
     assert len(m['gather_ms_per_rank']) == 2 and m['rank_devices'] == [0, 0]          # SPA_BENCH_SAME_DEVICE: both on cuda:0
     assert d['exact_fp32_value'] > 0 and d['dtype'].startswith('f32 as 2 x f16')
+    assert d['full'] and d['device_resident_value'] > 0                # --full: the device-resident loop ran too
 
 
 def test_bench_launches_its_own_ranks(tmp_path):
@@ -411,15 +412,16 @@ def test_bench_launches_its_own_ranks(tmp_path):
 
 def test_bench_dumps_the_same_outputs_run_after_run(tmp_path):
     """`bench.py --dump-outputs DIR` writes what the headline loop returned for its last batch; two runs with the same
-    arguments write the same arrays, and --steps is the number of timed steps."""
+    arguments write the same arrays, and --steps is the number of timed steps.  A plain run (no --full) measures the
+    headline loop alone."""
     import subprocess
     B, H, W, steps = 2, 128, 256, 3
     dumps = []
     for run in range(2):
         d = tmp_path / ('run%d' % run)
         cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1',
-               '--batch', str(B), '--height', str(H), '--width', str(W), '--n_slic_segments', '40', '--no_cpu_baseline',
-               '--no_exact_fp32', '--dump-outputs', str(d)]
+               '--batch', str(B), '--height', str(H), '--width', str(W), '--n_slic_segments', '40',
+               '--dump-outputs', str(d)]
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -428,6 +430,8 @@ def test_bench_dumps_the_same_outputs_run_after_run(tmp_path):
         assert line['steps'] == steps and line['ms_per_step'] > 0
         assert line['host_to_host']['images_downloaded'] == B * steps
         assert line['dumped_outputs']['dir'] == str(d)
+        assert not line['full'] and 'cpu_baseline' not in line
+        assert line['exact_fp32_value'] is None and line['device_resident_value'] is None
         dumps.append({p[:-4]: np.load(str(d / p)) for p in sorted(os.listdir(str(d)))})
     a, b = dumps
     assert sorted(a) == ['assignment', 'cluster', 'descriptors', 'features', 'n_superpixels', 'prior', 'road', 'superpixels']

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the raw outputs of tools/make_profiles.sh (under gpurun_out/) into the committed
+"""Turn the raw outputs of tools/make_profiles.sh (under $PROFILE_RAW, default build/profiles_raw) into the committed
 summaries under profiles/:  kernel-stats table of the default bench, the bench line, and the
 HBM-traffic table (+ a JSON with per-image traffic that bench.py reports as roofline.traffic)."""
 import csv
@@ -10,7 +10,7 @@ import re
 import sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-go = os.path.join(root, 'gpurun_out')
+go = os.environ.get('PROFILE_RAW') or os.path.join(root, 'build', 'profiles_raw')
 prof = os.path.join(root, 'profiles')
 tag = sys.argv[1] if len(sys.argv) > 1 else 'r4_final'
 
@@ -24,7 +24,7 @@ for r in ours:
     r['short'] = re.sub(r'^void ', '', r['Name']).split('(')[0]
 ours.sort(key=lambda r: -float(r['TotalDurationNs']))
 lines = ['# %s: rocprofv3 --kernel-trace --stats of the default bench' % tag,
-         'command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no_cpu_baseline --steps 20 --warmup 5',
+         'command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no_cpu_baseline --no_exact_fp32 --steps 20 --warmup 5',
          '(5 warm-up + 20 device-resident + 3 host-loop warm-up + 20 host-loop (the headline) steps of 30 images, 1024x2048, DRN-D-22 fp32, SLIC 200, '
          'mean pooling, k=2)', '',
          '## libspalign kernels (hand-written HIP)', '',
