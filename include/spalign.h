@@ -514,6 +514,22 @@ int spa_segnet_encode(spa_ctx *ctx, const float *x, int32_t x_layout, int32_t B,
 int spa_segnet_decode(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B, int32_t Hh,
                       int32_t Wh, const float *wt, const float *bias, const float *wc, const float *bc, float *y,
                       void *stream);
+/* The two stages on the bf16 matrix cores (labels_from_segnet.py --dtype bf16), with exactly the arguments, shapes,
+ * layouts, alignment rules and refusal codes of spa_segnet_encode / spa_segnet_decode.  Every product operand is the
+ * round-to-nearest-even bf16 of the float32 value the float32 stage multiplies at that point: the standardised,
+ * LRN-normalised conv1 input (computed with the float32 stage's operations), the map value or the unpooled value (zero
+ * where the index does not select the position), and the weight wt as given (rounded once per call into a packed bf16
+ * copy in the context workspace, stream-ordered).  The products accumulate in float32 (v_mfma_f32_16x16x32_bf16); the
+ * epilogue is the float32 stage's, in float32: bias, ReLU, 2x2 max-pool with the first maximum's index, and decode1's
+ * classifier and softmax.  pooled, idx and y keep the float32 stages' types, shapes and layouts, so spa_segnet_score
+ * takes decode1's output as it is.  No atomics: an image's outputs have the same bits whatever the batch size and its
+ * position in the batch. */
+int spa_segnet_encode_bf16(spa_ctx *ctx, const float *x, int32_t x_layout, int32_t B, int32_t H, int32_t W,
+                           int32_t Cin, const float *wt, const float *bias, const float *mean_host,
+                           const float *std_host, float *pooled, uint8_t *idx, void *stream);
+int spa_segnet_decode_bf16(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B, int32_t Hh,
+                           int32_t Wh, const float *wt, const float *bias, const float *wc, const float *bc, float *y,
+                           void *stream);
 /* SegNetBasic.predict's tail (segnet_basic.py:101-106): prob (B,2,h,w) float32 resized to (H,W) as chainercv's PIL
  * backend does it (Image.resize(BILINEAR) per channel, mode 'F': double coefficients, a horizontal pass rounded to
  * float32, then the vertical pass; same bits), mask (B,H,W) uint8 = argmax over the two channels (ties: 0), scores

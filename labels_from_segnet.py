@@ -9,8 +9,11 @@ Outputs per image, in --out_dir:
                           `pred` under this name too; kept byte-compatible.  save_labels(..., save_each=False) returns
                           the float32 (2, H, W) scores instead, as run_train_rounds.py expects.
   <basename>.png          the 3-panel figure (unless --no_figure)
-  result.json             one JSON line per image, the reference's keys in its order
-Additions: --no_figure, --batchsize (images per launch chain).  --gpu -1 (the reference's CPU mode) runs on device 0:
+  result.json             one JSON line per image, the reference's keys in its order (with --dtype bf16 one more key
+                          after them, "dtype": "bf16"; float32 lines are the reference's keys only)
+Additions: --no_figure, --batchsize (images per launch chain), --dtype {fp32,bf16} (the precision of the convolutions'
+operands: fp32, the default, the float32 matrix cores; bf16 every product operand rounded to bf16 with float32
+accumulation, see include/spalign.h spa_segnet_encode_bf16).  --gpu -1 (the reference's CPU mode) runs on device 0:
 there is no CPU path.  Only model 'basic' in the snapshot's args.txt is supported.
 """
 import argparse
@@ -52,16 +55,19 @@ def _save_figure(d, i, pred, label, out_dir):
 
 def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
                 start_index, end_index, soft_label, eval_shape,
-                save_each=False, figure=True, batchsize=4, result_fn=None, on_labels=None):
+                save_each=False, figure=True, batchsize=4, result_fn=None, on_labels=None, dtype='fp32'):
     """labels_from_segnet.py:24-153.  With save_each=False returns {<out_dir>/<basename>: bool mask,
     <out_dir>/<basename>_scores: float32 (2, H, W) probabilities at eval_shape}.  result_fn: the file the JSON lines
     are appended to (default <out_dir>/result.json; utils/run_train_rounds.py gives each labelling process its own).
     on_labels (save_each=False): called with (key, array) for the mask and then the scores of every image, in index
     order, instead of collecting them in the returned dict (which stays empty), so a long range needs the memory of
-    one batch only."""
+    one batch only.  dtype: 'fp32' (default) or 'bf16', the network's convolution precision (segnet.SegNetBasic);
+    bf16 adds "dtype": "bf16" to every JSON line."""
     import torch
     segnet = importlib.import_module('superpixel-align_amd.segnet')
     cli = importlib.import_module('superpixel-align_amd.cli')
+    if dtype not in segnet.DTYPES:
+        raise ValueError('save_labels: dtype must be one of %s, got %r' % (segnet.DTYPES, dtype))
     train_args = segnet.load_train_args(param_dir)
 
     if not os.path.exists(out_dir):
@@ -72,7 +78,7 @@ def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
 
     device = max(int(gpu), 0)
     torch.cuda.set_device(device)
-    model = segnet.SegNetBasic.from_snapshot(param_dir, iteration, pred_shape=eval_shape, device=device)
+    model = segnet.SegNetBasic.from_snapshot(param_dir, iteration, pred_shape=eval_shape, device=device, dtype=dtype)
     eng = model.engine
     in_shape = tuple(int(v) for v in train_args['input_shape'])
     eval_shape_t = tuple(int(v) for v in eval_shape)
@@ -152,6 +158,8 @@ def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
                     'save_each': save_each,
                 })
                 result_info.update({'train_args': train_args})
+                if dtype != 'fp32':
+                    result_info['dtype'] = dtype
                 print(json.dumps(result_info), file=fp)
     del model
     if not save_each:
@@ -172,6 +180,7 @@ def get_parser():
     parser.add_argument('--eval_shape', type=int, nargs=2, default=[1024, 2048])
     parser.add_argument('--no_figure', action='store_true', default=False)
     parser.add_argument('--batchsize', type=int, default=4)
+    parser.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
     return parser
 
 
@@ -180,4 +189,5 @@ if __name__ == '__main__':
     save_labels(
         args.param_dir, args.iteration, args.gpu, args.img_zip_fn,
         args.label_zip_fn, args.out_dir, args.start_index, args.end_index,
-        args.soft_label, args.eval_shape, True, figure=not args.no_figure, batchsize=args.batchsize)
+        args.soft_label, args.eval_shape, True, figure=not args.no_figure, batchsize=args.batchsize,
+        dtype=args.dtype)

@@ -88,7 +88,7 @@ enum {
     WS_SEGNET_BNPART,  // SegNet training forward: per-workgroup per-channel partial sums of y and y^2
     WS_SEGNET_WROT,    // SegNet training dgrad: the weights rotated 180 degrees, in/out channels swapped
     WS_SEGNET_WGRAD,   // SegNet training wgrad: the split-K partial weight gradients (chunk, 49, 64, Cp)
-    WS_SEGNET_WBF16,   // SegNet bf16 training forward / dgrad: the layer's weights rounded to bf16 (and rotated)
+    WS_SEGNET_WBF16,   // SegNet bf16 training forward / dgrad and bf16 inference: the weights rounded to bf16
     WS_COUNT
 };
 

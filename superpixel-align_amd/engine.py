@@ -819,6 +819,14 @@ class Engine(object):
         """One encoder stage, maxpool2x2_argmax(relu(conv7x7(x) + bias)): x (B,3,H,W) float32 planar image 0..255
         (conv1: standardised with mean / std and LRN-normalised in the load; wt (49,64,4)) or (B,64,H,W) channels-last
         (wt (49,64,64)) -> (pooled (B,64,H/2,W/2) float32, idx (B,64,H/2,W/2) uint8), both channels-last."""
+        return self._segnet_encode(self._lib.spa_segnet_encode, x, wt, bias, mean, std)
+
+    def segnet_encode_bf16(self, x, wt, bias, mean=None, std=None):
+        """segnet_encode on the bf16 matrix cores: the same float32 arguments and outputs, every product operand
+        rounded to bf16 (round to nearest even), float32 accumulation and epilogue."""
+        return self._segnet_encode(self._lib.spa_segnet_encode_bf16, x, wt, bias, mean, std)
+
+    def _segnet_encode(self, fn, x, wt, bias, mean, std):
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
         B, C, H, W = x.shape
         _req(wt, torch.float32, 'wt')
@@ -827,14 +835,22 @@ class Engine(object):
         idx = torch.empty((B, 64, H // 2, W // 2), dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
         m = (ctypes.c_float * 3)(*mean) if mean is not None else None
         s = (ctypes.c_float * 3)(*std) if std is not None else None
-        check(self._lib.spa_segnet_encode(self._ctx, _ptr(x), self._layout(x), B, H, W, C, _ptr(wt), _ptr(bias), m, s,
-                                          _ptr(pooled), _ptr(idx), self._s()))
+        check(fn(self._ctx, _ptr(x), self._layout(x), B, H, W, C, _ptr(wt), _ptr(bias), m, s, _ptr(pooled), _ptr(idx),
+                 self._s()))
         return pooled, idx
 
     def segnet_decode(self, x, idx, wt, bias, wc=None, bc=None):
         """One decoder stage, conv7x7(unpool(x, idx)) + bias: x (B,64,h,w) float32 and idx (B,64,h,w) uint8
         channels-last -> (B,64,2h,2w) float32 channels-last; with the classifier wc (2,64), bc (2) (decode1): softmax
         probabilities (B,2,2h,2w) float32 planar."""
+        return self._segnet_decode(self._lib.spa_segnet_decode, x, idx, wt, bias, wc, bc)
+
+    def segnet_decode_bf16(self, x, idx, wt, bias, wc=None, bc=None):
+        """segnet_decode on the bf16 matrix cores: the same float32 arguments and outputs, every product operand
+        rounded to bf16 (round to nearest even), float32 accumulation, bias, classifier and softmax."""
+        return self._segnet_decode(self._lib.spa_segnet_decode_bf16, x, idx, wt, bias, wc, bc)
+
+    def _segnet_decode(self, fn, x, idx, wt, bias, wc, bc):
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and idx.dtype == torch.uint8
         B, C, h, w = x.shape
         assert C == 64 and tuple(idx.shape) == tuple(x.shape)
@@ -849,8 +865,8 @@ class Engine(object):
         layout = self._layout(x)
         if self._layout(idx) != layout:
             raise SpalignError('segnet_decode: x and idx have different layouts')
-        check(self._lib.spa_segnet_decode(self._ctx, _ptr(x), _ptr(idx), layout, B, h, w, _ptr(wt), _ptr(bias),
-                                          _ptr(wc), _ptr(bc), _ptr(y), self._s()))
+        check(fn(self._ctx, _ptr(x), _ptr(idx), layout, B, h, w, _ptr(wt), _ptr(bias), _ptr(wc), _ptr(bc), _ptr(y),
+                 self._s()))
         return y
 
     def segnet_score(self, prob, shape, want_scores=False):

@@ -11,6 +11,9 @@ models/segnet_basic.py in test mode (BatchNorm with its running statistics, fold
 
 Every layer is one launch (include/spalign.h: spa_segnet_encode / spa_segnet_decode / spa_segnet_score); the dataset's
 standardisation happens inside conv1's load, so the device input is the cubic-resized image as float32 0..255.
+SegNetBasic(..., dtype='bf16') runs the convolutions on the bf16 matrix cores instead (spa_segnet_encode_bf16 /
+spa_segnet_decode_bf16: every product operand rounded to bf16, float32 accumulation and epilogue); the maps,
+probabilities and the score stay float32.
 """
 import glob
 import json
@@ -27,6 +30,7 @@ ENCODERS = ('conv1', 'conv2', 'conv3', 'conv4')
 DECODERS = ('conv_decode4', 'conv_decode3', 'conv_decode2', 'conv_decode1')
 LAYERS = ENCODERS + DECODERS
 BN_PARAMS = ('gamma', 'beta', 'avg_mean', 'avg_var')
+DTYPES = ('fp32', 'bf16')            # the convolutions' operand precisions (inference here, training in segnet_train)
 
 # 2 x multiply-adds per 512 x 1024 image, from the layer shapes (tools/segnet_bench.py prices kernel times with it)
 def layer_flops(H=512, W=1024):
@@ -229,11 +233,15 @@ def resize_bilinear_pil(score, shape):
 class SegNetBasic(object):
     """The folded, packed network on one GPU.  predict(imgs) takes the images as the device path feeds them: (B,3,H,W)
     float32 0..255 at the training input_shape (the dataset's cubic resize done, its standardisation NOT: conv1 applies
-    it in its load, with the same two float32 operations), H and W multiples of 16."""
+    it in its load, with the same two float32 operations), H and W multiples of 16.  dtype (DTYPES): 'fp32' the
+    float32 matrix-core convolutions, 'bf16' the bf16 ones (operands rounded to bf16, float32 accumulation)."""
 
-    def __init__(self, params, pred_shape=None, device=None, engine=None):
+    def __init__(self, params, pred_shape=None, device=None, engine=None, dtype='fp32'):
+        if dtype not in DTYPES:
+            raise ValueError('SegNetBasic: dtype must be one of %s, got %r' % (DTYPES, dtype))
         import torch
         from .engine import Engine
+        self.dtype = dtype
         self.engine = engine or Engine(device)
         dev = self.engine.device
         folded = fold_bn(params)
@@ -248,9 +256,11 @@ class SegNetBasic(object):
         self.pred_shape = tuple(int(v) for v in pred_shape) if pred_shape is not None else None
 
     @classmethod
-    def from_snapshot(cls, param_dir, iteration, pred_shape=None, device=None):
+    def from_snapshot(cls, param_dir, iteration, pred_shape=None, device=None, dtype='fp32'):
+        if dtype not in DTYPES:
+            raise ValueError('SegNetBasic: dtype must be one of %s, got %r' % (DTYPES, dtype))
         train_args, snapshot, params = load_snapshot(param_dir, iteration)
-        model = cls(params, pred_shape, device)
+        model = cls(params, pred_shape, device, dtype=dtype)
         model.train_args, model.snapshot = train_args, snapshot
         return model
 
@@ -262,19 +272,23 @@ class SegNetBasic(object):
         B, C, H, W = x.shape
         if C != 3 or H % 16 or W % 16:
             raise ValueError('SegNet-Basic input must be (B,3,H,W) with H, W multiples of 16, got %s' % (tuple(x.shape),))
+        if self.dtype == 'bf16':
+            encode, decode = e.segnet_encode_bf16, e.segnet_decode_bf16
+        else:
+            encode, decode = e.segnet_encode, e.segnet_decode
         h, pools = x, []
         for name in ENCODERS:
             timer and timer(name)
-            h, idx = e.segnet_encode(h, self.w[name], self.b[name], MEAN, STD)
+            h, idx = encode(h, self.w[name], self.b[name], MEAN, STD)
             pools.append(idx)
             if trace is not None:
                 trace.append((h, idx))
         for name, idx in zip(DECODERS, pools[::-1]):
             timer and timer(name)
             if name == 'conv_decode1':
-                h = e.segnet_decode(h, idx, self.w[name], self.b[name], self.wc, self.bc)
+                h = decode(h, idx, self.w[name], self.b[name], self.wc, self.bc)
             else:
-                h = e.segnet_decode(h, idx, self.w[name], self.b[name])
+                h = decode(h, idx, self.w[name], self.b[name])
         timer and timer(None)
         return h
 

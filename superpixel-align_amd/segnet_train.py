@@ -29,10 +29,9 @@ import zipfile
 import numpy as np
 
 from . import segnet
-from .segnet import BN_EPS, DECODERS, ENCODERS, LAYERS, MEAN, STD
+from .segnet import BN_EPS, DECODERS, DTYPES, ENCODERS, LAYERS, MEAN, STD
 
 BN_DECAY = 0.9
-DTYPES = ('fp32', 'bf16')
 DTYPE_KEY = 'extensions/dtype'        # the snapshot entry that records the dtype of the run that wrote it
 BETA_INIT = 0.001
 PARAM_KEYS = tuple([n + '/W' for n in LAYERS] + ['%s_bn/%s' % (n, p) for n in LAYERS for p in ('gamma', 'beta')]

@@ -1,11 +1,16 @@
 #!/usr/bin/env python
 """SegNet-Basic inference on the MI355X: per-layer device-event times of libspalign's kernels (spa_segnet_encode /
 _decode / _score) at B images of 512 x 1024 (evaluated at 1024 x 2048), images/s of the whole launch chain, and each
-layer's achieved TFLOP/s from the FLOPs its shape needs (segnet.layer_flops) against the 157.3 TF float32 matrix peak.
-The same layers as float32 torch.nn.functional.conv2d (MIOpen) plus separate max_pool2d / max_unpool2d on the GPU are
-timed as the library baseline.  Random weights: the time does not depend on the values.
+layer's achieved TFLOP/s from the FLOPs its shape needs (segnet.layer_flops) against the matrix peak of the dtype
+(PEAK_TF of tools/segnet_train_bench.py: 157.3 TF float32, 16 x that bf16).  The same layers as float32
+torch.nn.functional.conv2d (MIOpen) plus separate max_pool2d / max_unpool2d on the GPU are timed as the library
+baseline.  Random weights: the time does not depend on the values.
 
-  python tools/segnet_bench.py [--batch 4] [--iters 20] [--out profiles/segnet_bench.json]
+  python tools/segnet_bench.py [--dtype fp32|bf16] [--compare_fp32] [--batch 4] [--iters 20] [--out profiles/segnet_bench.json]
+
+--dtype bf16: the bf16 kernels (spa_segnet_encode_bf16 / _decode_bf16).  --compare_fp32 (with --dtype bf16): the
+float32 chain is timed in the same process, the two chains alternating over --rounds rounds, and reported under
+'fp32' with the ratio of the chain times.
 """
 import argparse
 import importlib
@@ -18,8 +23,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
 segnet = importlib.import_module('superpixel-align_amd.segnet')
-PEAK_TF = 157.3
+from segnet_train_bench import PEAK_TF  # noqa: E402  (per-dtype matrix peaks, TFLOP/s)
 
 
 def random_params(seed=0):
@@ -84,8 +90,38 @@ def timed(fn, iters):
     return {k: float(np.median([d[k] for d in per])) for k in per[0]}
 
 
+def chain_ms(chain, iters):
+    """ms per chain: events around whole chains, no per-layer events inside"""
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(iters):
+        chain()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters
+
+
+def report(dtype, a, layers, ms, flops):
+    peak = PEAK_TF[dtype]
+    res = {'what': 'SegNet-Basic inference, libspalign %s MFMA kernels' % ('float32' if dtype == 'fp32' else dtype),
+           'dtype': dtype, 'batch': a.batch, 'input': [a.H, a.W], 'eval_shape': [2 * a.H, 2 * a.W], 'iters': a.iters,
+           'chain_ms': ms, 'images_per_s': a.batch * 1000.0 / ms, 'peak_tflops_matrix': peak, 'layers': {}}
+    res['network_tflops'] = sum(flops.values()) / (ms * 1e-3) / 1e12
+    res['network_share_of_peak'] = res['network_tflops'] / peak
+    for k, t in layers.items():
+        row = {'ms': t}
+        if k in flops:
+            tf = flops[k] / (t * 1e-3) / 1e12
+            row.update(gflop=flops[k] / 1e9, tflops=tf, share_of_peak=tf / peak)
+        res['layers'][k] = row
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'])
+    ap.add_argument('--compare_fp32', action='store_true', help='with --dtype bf16: time the float32 chain too')
+    ap.add_argument('--rounds', type=int, default=3, help='alternations of the two chains under --compare_fp32')
     ap.add_argument('--batch', type=int, default=4)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
@@ -98,43 +134,46 @@ def main():
         raise SystemExit('segnet_bench: no GPU (nothing is measured without one)')
     torch.cuda.set_device(0)
     p = random_params()
-    model = segnet.SegNetBasic(p, pred_shape=(2 * a.H, 2 * a.W))
-    eng = model.engine
+    dtypes = [a.dtype] + (['fp32'] if a.compare_fp32 and a.dtype != 'fp32' else [])
+    models = {dt: segnet.SegNetBasic(p, pred_shape=(2 * a.H, 2 * a.W), dtype=dt) for dt in dtypes}
     g = torch.Generator(device='cuda').manual_seed(1)
     x = torch.randint(0, 256, (a.batch, 3, a.H, a.W), generator=g, device='cuda').float()
     flops = {k: v * a.batch * (a.H * a.W) / (512.0 * 1024.0) for k, v in segnet.layer_flops().items()}
 
-    def chain(t=None):
-        prob = model.forward(x, timer=t)
-        if t is not None:
-            t('score')
-        eng.segnet_score(prob, (2 * a.H, 2 * a.W))
-        if t is not None:
-            t(None)
+    def chain_of(model):
+        def chain(t=None):
+            prob = model.forward(x, timer=t)
+            if t is not None:
+                t('score')
+            model.engine.segnet_score(prob, (2 * a.H, 2 * a.W))
+            if t is not None:
+                t(None)
+        return chain
 
-    for _ in range(a.warmup):
-        chain()
+    chains = {dt: chain_of(m) for dt, m in models.items()}
+    for dt in dtypes:
+        for _ in range(a.warmup):
+            chains[dt]()
     torch.cuda.synchronize()
-    layers = timed(chain, a.iters)
-    # end to end: events around whole chains, no per-layer events inside
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(a.iters):
-        chain()
-    e.record()
-    torch.cuda.synchronize()
-    chain_ms = s.elapsed_time(e) / a.iters
-    res = {'what': 'SegNet-Basic inference, libspalign float32 MFMA kernels', 'batch': a.batch, 'input': [a.H, a.W],
-           'eval_shape': [2 * a.H, 2 * a.W], 'iters': a.iters, 'chain_ms': chain_ms,
-           'images_per_s': a.batch * 1000.0 / chain_ms, 'peak_tflops_f32_matrix': PEAK_TF, 'layers': {}}
-    total_flop = sum(flops.values())
-    res['network_tflops'] = total_flop / (chain_ms * 1e-3) / 1e12
-    for k, ms in layers.items():
-        row = {'ms': ms}
-        if k in flops:
-            tf = flops[k] / (ms * 1e-3) / 1e12
-            row.update(gflop=flops[k] / 1e9, tflops=tf, share_of_peak=tf / PEAK_TF)
-        res['layers'][k] = row
+    per_layer = {dt: [] for dt in dtypes}
+    per_chain = {dt: [] for dt in dtypes}
+    for _ in range(a.rounds if len(dtypes) > 1 else 1):
+        for dt in dtypes:
+            per_layer[dt].append(timed(chains[dt], a.iters))
+            per_chain[dt].append(chain_ms(chains[dt], a.iters))
+    out = {}
+    for dt in dtypes:
+        layers = {k: float(np.median([d[k] for d in per_layer[dt]])) for k in per_layer[dt][0]}
+        out[dt] = report(dt, a, layers, float(np.median(per_chain[dt])), flops)
+    res = out[a.dtype]
+    if a.dtype == 'fp32':
+        res['peak_tflops_f32_matrix'] = PEAK_TF['fp32']
+    if len(dtypes) > 1:
+        res['rounds'] = a.rounds
+        res['chain_ms_rounds'] = per_chain[a.dtype]
+        res['fp32'] = out['fp32']
+        res['fp32']['chain_ms_rounds'] = per_chain['fp32']
+        res['chain_ratio_to_fp32'] = res['chain_ms'] / out['fp32']['chain_ms']
     if not a.no_library:
         for _ in range(a.warmup):
             library_forward(p, x, lambda n: None)

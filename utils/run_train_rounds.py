@@ -27,8 +27,10 @@ takes its children with it (torchrun answers SIGTERM by stopping its ranks).
 
 Additions, defaulting to what the reference hard-codes: --input_shape, --val_img_zip, --val_label_zip,
 --val_eval_shape (the training rounds' validation shape: train_segnet.py's --eval_shape, whose default the reference
-leaves in place; the driver's own --eval_shape is the labelling shape only), --dtype, --n_labels (overrides the split's
-constant), --no_figure (the labellers' 3-panel figures), --child_timeout.
+leaves in place; the driver's own --eval_shape is the labelling shape only), --dtype (the training rounds' dtype
+only), --label_dtype (the labelling passes' convolution precision, labels_from_segnet.py --dtype; fp32 unless given,
+whatever --dtype is), --n_labels (overrides the split's constant), --no_figure (the labellers' 3-panel figures),
+--child_timeout.
 plan() computes the rounds, their commands, resume paths, result-directory prefixes and zip names without launching
 anything.
 """
@@ -84,6 +86,8 @@ def get_parser():
     parser.add_argument('--val_eval_shape', type=int, nargs=2, default=[1024, 2048],
                         help="train_segnet.py's --eval_shape: the shape of the training rounds' validation")
     parser.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
+    parser.add_argument('--label_dtype', type=str, default='fp32', choices=['fp32', 'bf16'],
+                        help="labels_from_segnet.py's --dtype for the labelling passes (independent of --dtype)")
     parser.add_argument('--n_labels', type=int, default=None, help='images to relabel (default: the split size)')
     parser.add_argument('--no_figure', action='store_true', default=False)
     parser.add_argument('--child_timeout', type=float, default=0,
@@ -303,7 +307,7 @@ def label_worker(spec):
         save_labels(spec['param_dir'], spec['iteration'], spec['device'], spec['img_zip_fn'], spec['label_zip_fn'],
                     spec['out_dir'], spec['start'], spec['end'], spec['soft_label'], spec['eval_shape'],
                     spec['save_each'], figure=spec['figure'], result_fn=os.path.join(spool, 'result.json'),
-                    on_labels=None if spec['save_each'] else spool_one)
+                    on_labels=None if spec['save_each'] else spool_one, dtype=spec['dtype'])
 
 
 def _child_main(target, arg, parent_pid):
@@ -382,7 +386,7 @@ def create_label_from_model(args, param_dir, iteration, out_dir, out_zip):
         specs.append({'device': 0 if same_device else i, 'param_dir': param_dir, 'iteration': iteration,
                       'img_zip_fn': args.img_zip_fn, 'label_zip_fn': args.label_zip_fn, 'out_dir': out_dir,
                       'start': start, 'end': end, 'soft_label': soft_label, 'eval_shape': list(args.eval_shape),
-                      'save_each': args.save_each, 'figure': not args.no_figure,
+                      'save_each': args.save_each, 'figure': not args.no_figure, 'dtype': args.label_dtype,
                       'spool': os.path.join(spool_root, 'w%d' % i)})
     run_workers(label_worker, specs, args.child_timeout)
     spools = [s['spool'] for s in specs]
