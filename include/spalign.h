@@ -576,6 +576,21 @@ int spa_segnet_train_dgrad_bf16(spa_ctx *ctx, const float *dy, const float *wt, 
 int spa_segnet_train_wgrad_bf16(spa_ctx *ctx, const float *dy, const float *x, const uint8_t *idx, int32_t x_layout,
                                 int32_t B, int32_t H, int32_t W, int32_t Cin, const float *mean_host,
                                 const float *std_host, float *dw, void *stream);
+/* The same three passes at float32 accuracy on the f16 matrix cores (train_segnet.py --split_planes), with the same
+ * arguments, shapes, layouts, alignments and refusals as the float32 entry points.  Each float32 operand tensor (the
+ * standardised, LRN-normalised conv1 input, the map or unpooled value, dy, the weight) is scaled by one power of two t,
+ * computed on the device inside the call, that brings its largest magnitude into [2^14, 2^15) (1 for an all-zero
+ * tensor), and carried as h = f16(t v), l = f16(t v - h); every product is h h + h l + l h, three
+ * v_mfma_f32_16x16x32_f16 accumulating in float32, unscaled exactly before y, dx, the BN sums and dw are formed as
+ * above.  The weights are split once per call into the context workspace (stream-ordered).  No atomics. */
+int spa_segnet_train_forward_f16x3(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B,
+                                   int32_t H, int32_t W, int32_t Cin, const float *wt, const float *mean_host,
+                                   const float *std_host, float *y, double *stats, void *stream);
+int spa_segnet_train_dgrad_f16x3(spa_ctx *ctx, const float *dy, const float *wt, const uint8_t *idx, int32_t B,
+                                 int32_t H, int32_t W, float *dx, void *stream);
+int spa_segnet_train_wgrad_f16x3(spa_ctx *ctx, const float *dy, const float *x, const uint8_t *idx, int32_t x_layout,
+                                 int32_t B, int32_t H, int32_t W, int32_t Cin, const float *mean_host,
+                                 const float *std_host, float *dw, void *stream);
 
 /* save_info() scoring (:398-405): per image confusion of road (B,npix) uint8 against
    gt (B,npix) int32 in {-1 ignore, 0, 1} -> out (B,4) int64 {TN, FP, FN, TP}.             */

@@ -146,6 +146,11 @@ PROTOTYPES = {
     'spa_segnet_train_dgrad_bf16': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
     'spa_segnet_train_wgrad_bf16': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p,
                                                    c_p, c_p]),
+    'spa_segnet_train_forward_f16x3': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p,
+                                                      c_p, c_p, c_p]),
+    'spa_segnet_train_dgrad_f16x3': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
+    'spa_segnet_train_wgrad_f16x3': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p,
+                                                    c_p, c_p]),
 }
 
 

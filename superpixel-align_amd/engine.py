@@ -909,6 +909,11 @@ class Engine(object):
         operand rounded to bf16 (round to nearest even), float32 accumulation."""
         return self._segnet_train_forward(self._lib.spa_segnet_train_forward_bf16, x, wt, idx, mean, std, stats, out)
 
+    def segnet_train_forward_f16x3(self, x, wt, idx=None, mean=None, std=None, stats=True, out=None):
+        """segnet_train_forward at float32 accuracy on the f16 matrix cores: the same float32 arguments and outputs,
+        every operand split into two scaled half-precision planes, three products per float32 product."""
+        return self._segnet_train_forward(self._lib.spa_segnet_train_forward_f16x3, x, wt, idx, mean, std, stats, out)
+
     def _segnet_train_forward(self, fn, x, wt, idx, mean, std, stats, out):
         layout, cin, H, W = self._train_input(x, idx)
         _req(wt, torch.float32, 'wt')
@@ -929,6 +934,10 @@ class Engine(object):
     def segnet_train_dgrad_bf16(self, dy, wt, idx=None, out=None):
         """segnet_train_dgrad with dy and the weight rounded to bf16, float32 accumulation."""
         return self._segnet_train_dgrad(self._lib.spa_segnet_train_dgrad_bf16, dy, wt, idx, out)
+
+    def segnet_train_dgrad_f16x3(self, dy, wt, idx=None, out=None):
+        """segnet_train_dgrad at float32 accuracy: dy and the weight as split planes on the f16 matrix cores."""
+        return self._segnet_train_dgrad(self._lib.spa_segnet_train_dgrad_f16x3, dy, wt, idx, out)
 
     def _segnet_train_dgrad(self, fn, dy, wt, idx, out):
         dy = _req(dy, torch.float32, 'dy')
@@ -954,6 +963,10 @@ class Engine(object):
     def segnet_train_wgrad_bf16(self, dy, x, idx=None, mean=None, std=None, out=None):
         """segnet_train_wgrad with dy and the input form rounded to bf16, float32 accumulation."""
         return self._segnet_train_wgrad(self._lib.spa_segnet_train_wgrad_bf16, dy, x, idx, mean, std, out)
+
+    def segnet_train_wgrad_f16x3(self, dy, x, idx=None, mean=None, std=None, out=None):
+        """segnet_train_wgrad at float32 accuracy: dy and the input form as split planes on the f16 matrix cores."""
+        return self._segnet_train_wgrad(self._lib.spa_segnet_train_wgrad_f16x3, dy, x, idx, mean, std, out)
 
     def _segnet_train_wgrad(self, fn, dy, x, idx, mean, std, out):
         dy = _req(dy, torch.float32, 'dy')

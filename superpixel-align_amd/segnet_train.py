@@ -20,6 +20,11 @@ the products accumulate in float32, and everything else -- the float32 master we
 classifier, the loss and the optimizers -- is the float32 path unchanged.  `reference_loss(..., bf16_operands=True)`
 restates that step in float64.
 
+split_planes (SegNetTrainer(..., split_planes=True), train_segnet.py --split_planes) runs the 7x7 passes of a float32
+step at float32 accuracy on the f16 matrix cores (csrc/spa_segnet_train_f16x3.hip): every operand tensor is scaled by a
+power of two and carried as two half-precision planes, three products per float32 product, float32 accumulation.
+Everything else is the float32 path unchanged; its float64 restatement is `reference_loss` with unrounded operands.
+
 Data parallelism (train_segnet.py --data_parallel, SegNetTrainer.set_group(RankGroup())): one rank per GPU under
 torchrun, BatchNorm over the union of the ranks' batches and the mean of the ranks' gradients; see RankGroup.
 """
@@ -33,6 +38,7 @@ from .segnet import BN_EPS, DECODERS, DTYPES, ENCODERS, LAYERS, MEAN, STD
 
 BN_DECAY = 0.9
 DTYPE_KEY = 'extensions/dtype'        # the snapshot entry that records the dtype of the run that wrote it
+SPLIT_PLANES_KEY = 'extensions/split_planes'   # present (True) only in snapshots of split-plane runs
 BETA_INIT = 0.001
 PARAM_KEYS = tuple([n + '/W' for n in LAYERS] + ['%s_bn/%s' % (n, p) for n in LAYERS for p in ('gamma', 'beta')]
                    + ['conv_classifier/W', 'conv_classifier/b'])
@@ -290,16 +296,16 @@ def _functions():
     torch = _torch()
 
     class Conv7(torch.autograd.Function):
-        """y = conv7x7(x; wp) on the kernels; backward: dgrad (not for conv1) and split-K wgrad.  bf16: the passes
-        on the bf16 matrix cores (same arguments, float32 in and out)."""
+        """y = conv7x7(x; wp) on the kernels; backward: dgrad (not for conv1) and split-K wgrad.  family '' (float32),
+        '_bf16' (the bf16 matrix cores) or '_f16x3' (split planes on the f16 matrix cores) names the Engine passes;
+        all three take the same arguments, float32 in and out."""
 
         @staticmethod
-        def forward(ctx, x, wp, idx, eng, bf16=False):
-            fwd = eng.segnet_train_forward_bf16 if bf16 else eng.segnet_train_forward
-            y, stats = fwd(x, wp, idx, MEAN, STD)
+        def forward(ctx, x, wp, idx, eng, family=''):
+            y, stats = getattr(eng, 'segnet_train_forward' + family)(x, wp, idx, MEAN, STD)
             ctx.save_for_backward(x, wp, idx)
             ctx.eng = eng
-            ctx.bf16 = bf16
+            ctx.family = family
             ctx.mark_non_differentiable(stats)
             return y, stats
 
@@ -307,8 +313,8 @@ def _functions():
         def backward(ctx, gy, _gstats):
             x, wp, idx = ctx.saved_tensors
             eng = ctx.eng
-            dgrad = eng.segnet_train_dgrad_bf16 if ctx.bf16 else eng.segnet_train_dgrad
-            wgrad = eng.segnet_train_wgrad_bf16 if ctx.bf16 else eng.segnet_train_wgrad
+            dgrad = getattr(eng, 'segnet_train_dgrad' + ctx.family)
+            wgrad = getattr(eng, 'segnet_train_wgrad' + ctx.family)
             gy = gy.contiguous()
             dx = None
             if ctx.needs_input_grad[0]:
@@ -352,11 +358,15 @@ _FN = []
 class SegNetTrainer(object):
     """Parameters, running statistics and the optimizer of one SegNetBasic on one GPU.  P: float32 tensors keyed as
     the snapshot (conv1/W, conv1_bn/gamma, ..., conv_classifier/b), S: the running statistics.  dtype 'fp32' or
-    'bf16': the operands of the 7x7 passes (see the module docstring); P, S and the optimizer are float32 in both."""
+    'bf16': the operands of the 7x7 passes (see the module docstring); P, S and the optimizer are float32 in both.
+    split_planes (float32 only): the 7x7 passes at float32 accuracy on the f16 matrix cores."""
 
-    def __init__(self, params, optimizer, lossfun, engine=None, device=None, dtype='fp32'):
+    def __init__(self, params, optimizer, lossfun, engine=None, device=None, dtype='fp32', split_planes=False):
         if dtype not in DTYPES:
             raise ValueError('SegNetTrainer: dtype must be one of %s, got %r' % (DTYPES, dtype))
+        if split_planes and dtype != 'fp32':
+            raise ValueError("SegNetTrainer: split_planes=True runs the float32 step on split planes; it does not "
+                             "combine with dtype=%r" % (dtype,))
         torch = _torch()
         from .engine import Engine
         if not _FN:
@@ -369,6 +379,8 @@ class SegNetTrainer(object):
         self.opt = optimizer
         self.lossfun = lossfun
         self.dtype = dtype
+        self.split_planes = bool(split_planes)
+        self.family = '_f16x3' if self.split_planes else ('_bf16' if dtype == 'bf16' else '')
         self.group = None           # a RankGroup: data-parallel steps (set_group)
 
     def set_group(self, group):
@@ -406,7 +418,7 @@ class SegNetTrainer(object):
             return BatchNorm.apply(y, P[name + '_bn/gamma'], P[name + '_bn/beta'], mean.float(), rstd, group)
 
         for name in ENCODERS:
-            y, stats = Conv7.apply(h, pack_w(P[name + '/W']), None, self.eng, self.dtype == 'bf16')
+            y, stats = Conv7.apply(h, pack_w(P[name + '/W']), None, self.eng, self.family)
             a = torch.relu(bn(name, y, stats))
             h, idx = pool_argmax_nhwc(a)
             h = h.contiguous()
@@ -414,7 +426,7 @@ class SegNetTrainer(object):
         if trace is not None:
             trace.extend(pools)
         for name, idx in zip(DECODERS, pools[::-1]):
-            y, stats = Conv7.apply(h, pack_w(P[name + '/W']), idx, self.eng, self.dtype == 'bf16')
+            y, stats = Conv7.apply(h, pack_w(P[name + '/W']), idx, self.eng, self.family)
             h = bn(name, y, stats)
         score = torch.matmul(h, P['conv_classifier/W'].view(2, 64).t()) + P['conv_classifier/b']
         return self.lossfun(score.permute(0, 3, 1, 2), t)
@@ -584,7 +596,8 @@ OPT = 'updater/optimizer:main/'
 def save_snapshot(path, trainer, iteration, lr, iterator_state, extra=None):
     """A Chainer-style npz: updater/model:main/predictor/<link>/<param> (what segnet.load_snapshot reads), the
     optimizer state under updater/optimizer:main/predictor/<link>/<param>/<state>, the iteration, lr, the iterator,
-    numpy's random state (so --resume continues bit for bit) and, under DTYPE_KEY, the trainer's dtype."""
+    numpy's random state (so --resume continues bit for bit), under DTYPE_KEY the trainer's dtype and, for a
+    split-plane trainer only, SPLIT_PLANES_KEY = True."""
     d = {}
     for k, v in trainer.params_numpy().items():
         d[segnet.PREFIX + k] = v
@@ -603,6 +616,8 @@ def save_snapshot(path, trainer, iteration, lr, iterator_state, extra=None):
     d['extensions/np_random/has_gauss'] = np.asarray(st[3])
     d['extensions/np_random/cached_gaussian'] = np.asarray(st[4])
     d[DTYPE_KEY] = np.asarray(getattr(trainer, 'dtype', 'fp32'))
+    if getattr(trainer, 'split_planes', False):
+        d[SPLIT_PLANES_KEY] = np.asarray(True)
     for k, v in (extra or {}).items():
         d[k] = np.asarray(v)
     tmp = path + '.tmp.npz'
@@ -615,6 +630,13 @@ def snapshot_dtype(path):
     Either kind resumes in either dtype: the master weights and the optimizer state are float32 in both."""
     with np.load(path) as z:
         return str(z[DTYPE_KEY]) if DTYPE_KEY in z.files else 'fp32'
+
+
+def snapshot_split_planes(path):
+    """Whether a snapshot was written by a split-plane run (False for one that does not record it).  The state is
+    float32 either way, so it resumes with or without --split_planes."""
+    with np.load(path) as z:
+        return bool(z[SPLIT_PLANES_KEY]) if SPLIT_PLANES_KEY in z.files else False
 
 
 def load_snapshot_state(path):

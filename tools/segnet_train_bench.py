@@ -5,7 +5,11 @@ dgrad, wgrad) with its TFLOP/s from the layer shape (segnet.layer_flops: forward
 forward FLOPs, wgrad too) against the matrix peak of the dtype: 157.3 TF float32, 16 x that (2516.8 TF dense) bf16.
 Random weights and inputs: the time does not depend on the values.
 
-  python tools/segnet_train_bench.py [--dtype fp32|bf16] [--batch 4] [--iters 10] [--out profiles/segnet_train_bench_b4.json]
+  python tools/segnet_train_bench.py [--dtype fp32|bf16] [--split_planes] [--batch 4] [--iters 10] [--out ...]
+
+--split_planes: the float32 step with its passes on split f16 planes (SegNetTrainer(split_planes=True)).  TFLOP/s
+count the float32 FLOPs; the share of peak is that of the 16-bit dense peak (2516.8 TF) at 3 f16 products per float32
+product.
 
 --data_parallel: the step of a data-parallel rank (segnet_train.RankGroup: BN statistics and gradients exchanged).
 Under SPA_DIST_FORCE=1 on one GPU that is one RCCL rank, which times the exchanges' own cost; under torchrun one rank
@@ -47,12 +51,15 @@ def main():
     ap.add_argument('--height', type=int, default=512)
     ap.add_argument('--width', type=int, default=1024)
     ap.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'])
+    ap.add_argument('--split_planes', action='store_true')
     ap.add_argument('--out', default=None)
     ap.add_argument('--data_parallel', action='store_true')
     a = ap.parse_args()
     B, H, W = a.batch, a.height, a.width
-    sfx = '_bf16' if a.dtype == 'bf16' else ''
-    peak = PEAK_TF[a.dtype]
+    if a.split_planes and a.dtype != 'fp32':
+        ap.error('--split_planes does not combine with --dtype %s' % a.dtype)
+    sfx = '_f16x3' if a.split_planes else ('_bf16' if a.dtype == 'bf16' else '')
+    peak = PEAK_TF['bf16'] / 3 if a.split_planes else PEAK_TF[a.dtype]     # float32 FLOP/s at 3 f16 products each
     group = None
     if a.data_parallel:
         dist = importlib.import_module('superpixel-align_amd.dist')
@@ -97,7 +104,7 @@ def main():
     torch.cuda.empty_cache()
     # the whole step
     tr = st.SegNetTrainer(st.init_params(0), st.MomentumSGD(0.01, weight_decay=0.0005), st.softmax_cross_entropy,
-                          engine=eng, dtype=a.dtype)
+                          engine=eng, dtype=a.dtype, split_planes=a.split_planes)
     tr.set_group(group)
     img = torch.rand((B, 3, H, W), generator=g, device='cuda') * 255
     t = torch.randint(0, 2, (B, H, W), generator=g, device='cuda')
@@ -113,7 +120,10 @@ def main():
     out = {'batch': B, 'input': [H, W], 'step_ms': step_ms, 'images_per_s': B * 1000.0 / step_ms,
            'conv_kernels_ms': kern_ms, 'conv_tflop_per_step': total_f / 1e12,
            'conv_tflops': total_f / (kern_ms * 1e-3) / 1e12, 'step_tflops': total_f / (step_ms * 1e-3) / 1e12}
-    if a.dtype == 'fp32':
+    if a.split_planes:
+        out.update({'split_planes': True, 'peak_tflops_f16_matrix': PEAK_TF['bf16'], 'f16_products_per_f32_product': 3,
+                    'conv_share_of_peak': out['conv_tflops'] / peak, 'step_outside_conv_kernels_ms': step_ms - kern_ms})
+    elif a.dtype == 'fp32':
         out['peak_tflops_f32_matrix'] = peak
     else:
         out.update({'dtype': 'bf16', 'peak_tflops_bf16_matrix': peak, 'conv_share_of_peak': out['conv_tflops'] / peak,

@@ -20,6 +20,12 @@ the snapshot's own dtype, and a float32 snapshot may also be resumed in bf16 or 
 optimizer state are float32 in both).  Validation always runs the float32 inference network, and labels_from_segnet.py
 reads the snapshots of either dtype.
 
+--split_planes (also parsed in front of the reference flags): run every 7x7 convolution pass of the float32 step at
+float32 accuracy on the f16 matrix cores (each operand as two power-of-two-scaled half-precision planes, three products
+per float32 product).  Everything else is the float32 path.  It does not combine with --dtype bf16.  Only when given,
+args.txt records "split_planes": true and every snapshot an extensions/split_planes entry; --resume follows the
+command-line flag (the state is float32 either way), and labels_from_segnet.py reads the snapshots unchanged.
+
 --data_parallel (also parsed in front of the reference flags): run as one rank of a torchrun launch (RANK, WORLD_SIZE,
 LOCAL_RANK; dist.init binds the rank's GPU), what the reference does under mpiexec with ChainerMN.  A step computes
 the gradient of the mean of the ranks' losses with BatchNorm over all ranks' batches (segnet_train.RankGroup).  Rank
@@ -102,15 +108,38 @@ def get_dtype_args(argv=None):
 
 
 def get_pre_args(argv=None):
-    """-> (namespace of this implementation's flags, the remaining arguments for get_args): --dtype (get_dtype_args)
-    and --data_parallel, read by one pre-parser in front of the reference flag set of get_parser."""
+    """-> (namespace of this implementation's flags, the remaining arguments for get_args): --dtype (get_dtype_args),
+    --split_planes and --data_parallel, read by one pre-parser in front of the reference flag set of get_parser."""
     argv = list(sys.argv[1:] if argv is None else argv)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'],
                      help='operands of the 7x7 convolution passes: float32 or bf16 (float32 accumulation)')
+    pre.add_argument('--split_planes', action='store_true', default=False,
+                     help='float32 step with its 7x7 passes at float32 accuracy on the f16 matrix cores')
     pre.add_argument('--data_parallel', action='store_true', default=False,
                      help='run as one rank of a torchrun launch (RANK / WORLD_SIZE / LOCAL_RANK)')
     return pre.parse_known_args(argv)
+
+
+def check_split_planes(pre):
+    """The refusal of --split_planes with --dtype bf16 (the mode is the float32 step on split planes)."""
+    if pre.split_planes and pre.dtype != 'fp32':
+        raise ValueError('--split_planes runs the float32 step on split f16 planes and does not combine with '
+                         '--dtype %s' % pre.dtype)
+
+
+def run_args(argv=None):
+    """-> (the pre-parser's namespace, the run's arguments as args.txt records them, before a data-parallel run adds
+    its world size): the reference flags plus dtype, and split_planes / data_parallel only where they are given."""
+    pre, argv = get_pre_args(argv)
+    check_split_planes(pre)
+    args = get_args(argv)
+    args.dtype = pre.dtype
+    if pre.split_planes:
+        args.split_planes = True                   # args.txt records it; a default run's args.txt is unchanged
+    if pre.data_parallel:
+        args.data_parallel = True                  # args.txt records it with the world size; one-process runs unchanged
+    return pre, args
 
 
 def create_result_dir(prefix):
@@ -189,12 +218,8 @@ def resume_check(snapshot_world_size, world_size):
 
 def main(argv=None):
     import torch
-    pre, argv = get_pre_args(argv)
-    args = get_args(argv)
-    args.dtype = pre.dtype
+    pre, args = run_args(argv)
     dp = pre.data_parallel
-    if dp:
-        args.data_parallel = True                  # args.txt records it with the world size; one-process runs unchanged
     check_supported(args)
     st = importlib.import_module('superpixel-align_amd.segnet_train')
     segnet = importlib.import_module('superpixel-align_amd.segnet')
@@ -242,7 +267,8 @@ def main(argv=None):
     else:
         opt = st.MomentumSGD(args.lr, weight_decay=args.weight_decay)
     device = torch.cuda.current_device()
-    trainer = st.SegNetTrainer(st.init_params(0), opt, lossfun, engine=eng, device=device, dtype=args.dtype)
+    trainer = st.SegNetTrainer(st.init_params(0), opt, lossfun, engine=eng, device=device, dtype=args.dtype,
+                               split_planes=pre.split_planes)
     it = st.ShuffledIterator(len(train_ids), args.batchsize)
 
     result_dir = None
@@ -261,7 +287,10 @@ def main(argv=None):
         snap_dtype = st.snapshot_dtype(args.resume)
         if snap_dtype != args.dtype and rank == 0:
             print('resuming a %s snapshot in %s' % (snap_dtype, args.dtype))
-        trainer = st.SegNetTrainer(params, opt, lossfun, engine=trainer.eng, dtype=args.dtype)
+        if st.snapshot_split_planes(args.resume) != pre.split_planes and rank == 0:
+            print('resuming a %s snapshot %s --split_planes' % (snap_dtype, 'with' if pre.split_planes else 'without'))
+        trainer = st.SegNetTrainer(params, opt, lossfun, engine=trainer.eng, dtype=args.dtype,
+                                   split_planes=pre.split_planes)
         opt.t = t
         if args.optimizer == 'MomentumSGD':
             opt.lr = lr

@@ -29,8 +29,9 @@ Additions, defaulting to what the reference hard-codes: --input_shape, --val_img
 --val_eval_shape (the training rounds' validation shape: train_segnet.py's --eval_shape, whose default the reference
 leaves in place; the driver's own --eval_shape is the labelling shape only), --dtype (the training rounds' dtype
 only), --label_dtype (the labelling passes' convolution precision, labels_from_segnet.py --dtype; fp32 unless given,
-whatever --dtype is), --n_labels (overrides the split's constant), --no_figure (the labellers' 3-panel figures),
---child_timeout.
+whatever --dtype is), --split_planes (the training rounds' train_segnet.py --split_planes: float32 steps with their
+convolution passes on split f16 planes; passed to the training children only when given), --n_labels (overrides the
+split's constant), --no_figure (the labellers' 3-panel figures), --child_timeout.
 plan() computes the rounds, their commands, resume paths, result-directory prefixes and zip names without launching
 anything.
 """
@@ -88,6 +89,8 @@ def get_parser():
     parser.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
     parser.add_argument('--label_dtype', type=str, default='fp32', choices=['fp32', 'bf16'],
                         help="labels_from_segnet.py's --dtype for the labelling passes (independent of --dtype)")
+    parser.add_argument('--split_planes', action='store_true', default=False,
+                        help="train_segnet.py --split_planes for the training rounds (float32 only)")
     parser.add_argument('--n_labels', type=int, default=None, help='images to relabel (default: the split size)')
     parser.add_argument('--no_figure', action='store_true', default=False)
     parser.add_argument('--child_timeout', type=float, default=0,
@@ -96,7 +99,10 @@ def get_parser():
 
 
 def get_args(argv=None):
-    args = get_parser().parse_args(argv)
+    parser = get_parser()
+    args = parser.parse_args(argv)
+    if args.split_planes and args.dtype != 'fp32':
+        parser.error('--split_planes (float32 steps on split planes) does not combine with --dtype %s' % args.dtype)
     n_labels = args.n_labels
     if args.test_mode:
         args.iteration = 10
@@ -197,6 +203,8 @@ def train_argv(args, step, result_dir, dirs):
         a += ['--n_use_data', str(args.n_use_data)]
     if args.random:
         a.append('--random')
+    if args.split_planes:
+        a.append('--split_planes')
     return a
 
 
