@@ -530,6 +530,22 @@ int spa_segnet_encode_bf16(spa_ctx *ctx, const float *x, int32_t x_layout, int32
 int spa_segnet_decode_bf16(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B, int32_t Hh,
                            int32_t Wh, const float *wt, const float *bias, const float *wc, const float *bc, float *y,
                            void *stream);
+/* The two stages at float32 accuracy on the f16 matrix cores (labels_from_segnet.py --split_planes), with exactly the
+ * arguments, shapes, layouts, alignment rules and refusal codes of spa_segnet_encode / spa_segnet_decode.  Each operand
+ * -- the conv1 input as the float32 stage computes it, the map, a decoder's pooled map, the weight wt as given -- is
+ * scaled by a power of two 2^k that brings its largest magnitude into [2^14, 2^15) (computed on the device inside the
+ * call; one k for the weights, one PER IMAGE for the activations; k = 0 for an all-zero operand) and carried as two
+ * half-precision planes h = f16(2^k v), l = f16(2^k v - h).  A product is h h + h l + l h on v_mfma_f32_16x16x32_f16
+ * with float32 accumulation, the cross terms in accumulators of their own; the sum is unscaled exactly before the bias
+ * is added, and the epilogue is the float32 stage's, in float32.  The weights are split once per call into the context
+ * workspace, stream-ordered.  pooled, idx and y keep the float32 stages' types, shapes and layouts.  No atomics: an
+ * image's outputs have the same bits whatever the batch size and its position in the batch. */
+int spa_segnet_encode_f16x3(spa_ctx *ctx, const float *x, int32_t x_layout, int32_t B, int32_t H, int32_t W,
+                            int32_t Cin, const float *wt, const float *bias, const float *mean_host,
+                            const float *std_host, float *pooled, uint8_t *idx, void *stream);
+int spa_segnet_decode_f16x3(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B, int32_t Hh,
+                            int32_t Wh, const float *wt, const float *bias, const float *wc, const float *bc, float *y,
+                            void *stream);
 /* SegNetBasic.predict's tail (segnet_basic.py:101-106): prob (B,2,h,w) float32 resized to (H,W) as chainercv's PIL
  * backend does it (Image.resize(BILINEAR) per channel, mode 'F': double coefficients, a horizontal pass rounded to
  * float32, then the vertical pass; same bits), mask (B,H,W) uint8 = argmax over the two channels (ties: 0), scores

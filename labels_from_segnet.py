@@ -10,10 +10,13 @@ Outputs per image, in --out_dir:
                           the float32 (2, H, W) scores instead, as run_train_rounds.py expects.
   <basename>.png          the 3-panel figure (unless --no_figure)
   result.json             one JSON line per image, the reference's keys in its order (with --dtype bf16 one more key
-                          after them, "dtype": "bf16"; float32 lines are the reference's keys only)
+                          after them, "dtype": "bf16"; with --split_planes one more, "split_planes": true; plain float32
+                          lines are the reference's keys only)
 Additions: --no_figure, --batchsize (images per launch chain), --dtype {fp32,bf16} (the precision of the convolutions'
 operands: fp32, the default, the float32 matrix cores; bf16 every product operand rounded to bf16 with float32
-accumulation, see include/spalign.h spa_segnet_encode_bf16).  --gpu -1 (the reference's CPU mode) runs on device 0:
+accumulation, see include/spalign.h spa_segnet_encode_bf16), --split_planes (float32 accuracy on the f16 matrix cores:
+every operand as two scaled half-precision planes, three products per float32 product, spa_segnet_encode_f16x3; the
+counterpart of train_segnet.py --split_planes, refused with --dtype bf16).  --gpu -1 (the reference's CPU mode) runs on device 0:
 there is no CPU path.  Only model 'basic' in the snapshot's args.txt is supported.
 """
 import argparse
@@ -55,19 +58,20 @@ def _save_figure(d, i, pred, label, out_dir):
 
 def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
                 start_index, end_index, soft_label, eval_shape,
-                save_each=False, figure=True, batchsize=4, result_fn=None, on_labels=None, dtype='fp32'):
+                save_each=False, figure=True, batchsize=4, result_fn=None, on_labels=None,
+                split_planes=False, dtype='fp32'):
     """labels_from_segnet.py:24-153.  With save_each=False returns {<out_dir>/<basename>: bool mask,
     <out_dir>/<basename>_scores: float32 (2, H, W) probabilities at eval_shape}.  result_fn: the file the JSON lines
     are appended to (default <out_dir>/result.json; utils/run_train_rounds.py gives each labelling process its own).
     on_labels (save_each=False): called with (key, array) for the mask and then the scores of every image, in index
     order, instead of collecting them in the returned dict (which stays empty), so a long range needs the memory of
     one batch only.  dtype: 'fp32' (default) or 'bf16', the network's convolution precision (segnet.SegNetBasic);
-    bf16 adds "dtype": "bf16" to every JSON line."""
+    bf16 adds "dtype": "bf16" to every JSON line.  split_planes (dtype 'fp32' only): the float32-accurate
+    convolutions on the f16 matrix cores; adds "split_planes": true to every JSON line."""
     import torch
     segnet = importlib.import_module('superpixel-align_amd.segnet')
     cli = importlib.import_module('superpixel-align_amd.cli')
-    if dtype not in segnet.DTYPES:
-        raise ValueError('save_labels: dtype must be one of %s, got %r' % (segnet.DTYPES, dtype))
+    segnet.check_mode('save_labels', dtype, split_planes)
     train_args = segnet.load_train_args(param_dir)
 
     if not os.path.exists(out_dir):
@@ -78,7 +82,8 @@ def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
 
     device = max(int(gpu), 0)
     torch.cuda.set_device(device)
-    model = segnet.SegNetBasic.from_snapshot(param_dir, iteration, pred_shape=eval_shape, device=device, dtype=dtype)
+    model = segnet.SegNetBasic.from_snapshot(param_dir, iteration, pred_shape=eval_shape, device=device, dtype=dtype,
+                                             split_planes=split_planes)
     eng = model.engine
     in_shape = tuple(int(v) for v in train_args['input_shape'])
     eval_shape_t = tuple(int(v) for v in eval_shape)
@@ -160,6 +165,8 @@ def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
                 result_info.update({'train_args': train_args})
                 if dtype != 'fp32':
                     result_info['dtype'] = dtype
+                if split_planes:
+                    result_info['split_planes'] = True
                 print(json.dumps(result_info), file=fp)
     del model
     if not save_each:
@@ -181,13 +188,17 @@ def get_parser():
     parser.add_argument('--no_figure', action='store_true', default=False)
     parser.add_argument('--batchsize', type=int, default=4)
     parser.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
+    parser.add_argument('--split_planes', action='store_true', default=False)
     return parser
 
 
 if __name__ == '__main__':
-    args = get_parser().parse_args()
+    parser = get_parser()
+    args = parser.parse_args()
+    if args.split_planes and args.dtype != 'fp32':
+        parser.error('--split_planes is the float32-accurate mode: it cannot be combined with --dtype %s' % args.dtype)
     save_labels(
         args.param_dir, args.iteration, args.gpu, args.img_zip_fn,
         args.label_zip_fn, args.out_dir, args.start_index, args.end_index,
         args.soft_label, args.eval_shape, True, figure=not args.no_figure, batchsize=args.batchsize,
-        dtype=args.dtype)
+        split_planes=args.split_planes, dtype=args.dtype)

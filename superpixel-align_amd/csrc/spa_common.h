@@ -89,8 +89,8 @@ enum {
     WS_SEGNET_WROT,    // SegNet training dgrad: the weights rotated 180 degrees, in/out channels swapped
     WS_SEGNET_WGRAD,   // SegNet training wgrad: the split-K partial weight gradients (chunk, 49, 64, Cp)
     WS_SEGNET_WBF16,   // SegNet bf16 training forward / dgrad and bf16 inference: the weights rounded to bf16
-    WS_SEGNET_WF16X3,  // SegNet split-plane training forward / dgrad: the weights as two scaled f16 planes
-    WS_SEGNET_AMAX,    // SegNet split-plane training: per-workgroup maxima and the two operands' scale exponents
+    WS_SEGNET_WF16X3,  // SegNet split-plane training forward / dgrad and inference: the weights as two scaled f16 planes
+    WS_SEGNET_AMAX,    // SegNet split-plane training and inference: per-workgroup maxima and the operands' scale exponents
     WS_COUNT
 };
 

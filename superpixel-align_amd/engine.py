@@ -826,6 +826,11 @@ class Engine(object):
         rounded to bf16 (round to nearest even), float32 accumulation and epilogue."""
         return self._segnet_encode(self._lib.spa_segnet_encode_bf16, x, wt, bias, mean, std)
 
+    def segnet_encode_f16x3(self, x, wt, bias, mean=None, std=None):
+        """segnet_encode at float32 accuracy on the f16 matrix cores: the same float32 arguments and outputs, every
+        operand as two scaled half-precision planes (one scale per image), three products per float32 product."""
+        return self._segnet_encode(self._lib.spa_segnet_encode_f16x3, x, wt, bias, mean, std)
+
     def _segnet_encode(self, fn, x, wt, bias, mean, std):
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
         B, C, H, W = x.shape
@@ -849,6 +854,11 @@ class Engine(object):
         """segnet_decode on the bf16 matrix cores: the same float32 arguments and outputs, every product operand
         rounded to bf16 (round to nearest even), float32 accumulation, bias, classifier and softmax."""
         return self._segnet_decode(self._lib.spa_segnet_decode_bf16, x, idx, wt, bias, wc, bc)
+
+    def segnet_decode_f16x3(self, x, idx, wt, bias, wc=None, bc=None):
+        """segnet_decode at float32 accuracy on the f16 matrix cores: the same float32 arguments and outputs, every
+        operand as two scaled half-precision planes (one scale per image), float32 bias, classifier and softmax."""
+        return self._segnet_decode(self._lib.spa_segnet_decode_f16x3, x, idx, wt, bias, wc, bc)
 
     def _segnet_decode(self, fn, x, idx, wt, bias, wc, bc):
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and idx.dtype == torch.uint8

@@ -13,7 +13,9 @@ Every layer is one launch (include/spalign.h: spa_segnet_encode / spa_segnet_dec
 standardisation happens inside conv1's load, so the device input is the cubic-resized image as float32 0..255.
 SegNetBasic(..., dtype='bf16') runs the convolutions on the bf16 matrix cores instead (spa_segnet_encode_bf16 /
 spa_segnet_decode_bf16: every product operand rounded to bf16, float32 accumulation and epilogue); the maps,
-probabilities and the score stay float32.
+probabilities and the score stay float32.  SegNetBasic(..., split_planes=True) (dtype 'fp32' only) keeps float32
+accuracy on the f16 matrix cores (spa_segnet_encode_f16x3 / spa_segnet_decode_f16x3: every operand as two scaled
+half-precision planes, one scale per image, three products per float32 product).
 """
 import glob
 import json
@@ -31,6 +33,16 @@ DECODERS = ('conv_decode4', 'conv_decode3', 'conv_decode2', 'conv_decode1')
 LAYERS = ENCODERS + DECODERS
 BN_PARAMS = ('gamma', 'beta', 'avg_mean', 'avg_var')
 DTYPES = ('fp32', 'bf16')            # the convolutions' operand precisions (inference here, training in segnet_train)
+
+
+def check_mode(who, dtype, split_planes):
+    """The refusals every entry to the network shares: an unknown dtype, and split_planes with a dtype other than
+    'fp32' (the split-plane form is a float32-accurate computation; there is no bf16 variant of it)."""
+    if dtype not in DTYPES:
+        raise ValueError('%s: dtype must be one of %s, got %r' % (who, DTYPES, dtype))
+    if split_planes and dtype != 'fp32':
+        raise ValueError("%s: split_planes=True needs dtype='fp32', got dtype=%r" % (who, dtype))
+
 
 # 2 x multiply-adds per 512 x 1024 image, from the layer shapes (tools/segnet_bench.py prices kernel times with it)
 def layer_flops(H=512, W=1024):
@@ -234,14 +246,15 @@ class SegNetBasic(object):
     """The folded, packed network on one GPU.  predict(imgs) takes the images as the device path feeds them: (B,3,H,W)
     float32 0..255 at the training input_shape (the dataset's cubic resize done, its standardisation NOT: conv1 applies
     it in its load, with the same two float32 operations), H and W multiples of 16.  dtype (DTYPES): 'fp32' the
-    float32 matrix-core convolutions, 'bf16' the bf16 ones (operands rounded to bf16, float32 accumulation)."""
+    float32 matrix-core convolutions, 'bf16' the bf16 ones (operands rounded to bf16, float32 accumulation).
+    split_planes (with dtype 'fp32' only): the float32-accurate convolutions on the f16 matrix cores."""
 
-    def __init__(self, params, pred_shape=None, device=None, engine=None, dtype='fp32'):
-        if dtype not in DTYPES:
-            raise ValueError('SegNetBasic: dtype must be one of %s, got %r' % (DTYPES, dtype))
+    def __init__(self, params, pred_shape=None, device=None, engine=None, dtype='fp32', split_planes=False):
+        check_mode('SegNetBasic', dtype, split_planes)
         import torch
         from .engine import Engine
         self.dtype = dtype
+        self.split_planes = bool(split_planes)
         self.engine = engine or Engine(device)
         dev = self.engine.device
         folded = fold_bn(params)
@@ -256,11 +269,10 @@ class SegNetBasic(object):
         self.pred_shape = tuple(int(v) for v in pred_shape) if pred_shape is not None else None
 
     @classmethod
-    def from_snapshot(cls, param_dir, iteration, pred_shape=None, device=None, dtype='fp32'):
-        if dtype not in DTYPES:
-            raise ValueError('SegNetBasic: dtype must be one of %s, got %r' % (DTYPES, dtype))
+    def from_snapshot(cls, param_dir, iteration, pred_shape=None, device=None, dtype='fp32', split_planes=False):
+        check_mode('SegNetBasic', dtype, split_planes)
         train_args, snapshot, params = load_snapshot(param_dir, iteration)
-        model = cls(params, pred_shape, device, dtype=dtype)
+        model = cls(params, pred_shape, device, dtype=dtype, split_planes=split_planes)
         model.train_args, model.snapshot = train_args, snapshot
         return model
 
@@ -274,6 +286,8 @@ class SegNetBasic(object):
             raise ValueError('SegNet-Basic input must be (B,3,H,W) with H, W multiples of 16, got %s' % (tuple(x.shape),))
         if self.dtype == 'bf16':
             encode, decode = e.segnet_encode_bf16, e.segnet_decode_bf16
+        elif self.split_planes:
+            encode, decode = e.segnet_encode_f16x3, e.segnet_decode_f16x3
         else:
             encode, decode = e.segnet_encode, e.segnet_decode
         h, pools = x, []

@@ -454,9 +454,10 @@ class SegNetTrainer(object):
             out[n + '_bn/N'] = np.asarray(self.N[n])
         return out
 
-    def predictor(self, pred_shape=None):
-        """The inference network (BN folded from the running statistics) on the same engine."""
-        return segnet.SegNetBasic(self.params_numpy(), pred_shape, engine=self.eng)
+    def predictor(self, pred_shape=None, split_planes=False):
+        """The inference network (BN folded from the running statistics) on the same engine: the float32 one whatever
+        the training mode, or with split_planes its float32-accurate form on the f16 matrix cores."""
+        return segnet.SegNetBasic(self.params_numpy(), pred_shape, engine=self.eng, split_planes=split_planes)
 
 
 # ------------------------------------------------------------------------------- data parallelism

@@ -6,11 +6,17 @@ layer's achieved TFLOP/s from the FLOPs its shape needs (segnet.layer_flops) aga
 torch.nn.functional.conv2d (MIOpen) plus separate max_pool2d / max_unpool2d on the GPU are timed as the library
 baseline.  Random weights: the time does not depend on the values.
 
-  python tools/segnet_bench.py [--dtype fp32|bf16] [--compare_fp32] [--batch 4] [--iters 20] [--out profiles/segnet_bench.json]
+  python tools/segnet_bench.py [--dtype fp32|bf16] [--split_planes] [--compare_fp32 | --compare_all] [--batch 4]
+                               [--iters 20] [--out profiles/segnet_bench.json]
 
---dtype bf16: the bf16 kernels (spa_segnet_encode_bf16 / _decode_bf16).  --compare_fp32 (with --dtype bf16): the
-float32 chain is timed in the same process, the two chains alternating over --rounds rounds, and reported under
-'fp32' with the ratio of the chain times.
+--dtype bf16: the bf16 kernels (spa_segnet_encode_bf16 / _decode_bf16).  --split_planes (refused with --dtype bf16):
+the float32-accurate kernels on the f16 matrix cores (spa_segnet_encode_f16x3 / _decode_f16x3), reported as mode
+'f16x3' and priced against PEAK_TF['bf16'] / 3 (three f16 products per float32 product; the f16 and bf16 matrix peaks
+are equal), as tools/segnet_train_bench.py prices the training passes.  --compare_fp32 (with --dtype bf16 or
+--split_planes): the float32 chain is timed in the same process, the two chains alternating over --rounds rounds, and
+reported under 'fp32' with the ratio of the chain times.  --compare_all: all three modes alternate round by round in
+one process; the mode asked for is the top-level report, the other two follow under their names, each with its chain
+ms per round and its ratio to the float32 chain.
 """
 import argparse
 import importlib
@@ -101,10 +107,15 @@ def chain_ms(chain, iters):
     return s.elapsed_time(e) / iters
 
 
-def report(dtype, a, layers, ms, flops):
-    peak = PEAK_TF[dtype]
-    res = {'what': 'SegNet-Basic inference, libspalign %s MFMA kernels' % ('float32' if dtype == 'fp32' else dtype),
-           'dtype': dtype, 'batch': a.batch, 'input': [a.H, a.W], 'eval_shape': [2 * a.H, 2 * a.W], 'iters': a.iters,
+MODES = ('fp32', 'bf16', 'f16x3')
+MODE_PEAK = {'fp32': PEAK_TF['fp32'], 'bf16': PEAK_TF['bf16'], 'f16x3': PEAK_TF['bf16'] / 3}
+MODE_NAME = {'fp32': 'float32', 'bf16': 'bf16', 'f16x3': 'split-plane f16 (float32-accurate)'}
+
+
+def report(mode, a, layers, ms, flops):
+    peak = MODE_PEAK[mode]
+    res = {'what': 'SegNet-Basic inference, libspalign %s MFMA kernels' % MODE_NAME[mode],
+           'dtype': 'bf16' if mode == 'bf16' else 'fp32', 'split_planes': mode == 'f16x3', 'batch': a.batch, 'input': [a.H, a.W], 'eval_shape': [2 * a.H, 2 * a.W], 'iters': a.iters,
            'chain_ms': ms, 'images_per_s': a.batch * 1000.0 / ms, 'peak_tflops_matrix': peak, 'layers': {}}
     res['network_tflops'] = sum(flops.values()) / (ms * 1e-3) / 1e12
     res['network_share_of_peak'] = res['network_tflops'] / peak
@@ -120,8 +131,11 @@ def report(dtype, a, layers, ms, flops):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'])
-    ap.add_argument('--compare_fp32', action='store_true', help='with --dtype bf16: time the float32 chain too')
-    ap.add_argument('--rounds', type=int, default=3, help='alternations of the two chains under --compare_fp32')
+    ap.add_argument('--split_planes', action='store_true', help='the float32-accurate kernels on the f16 matrix cores')
+    ap.add_argument('--compare_fp32', action='store_true',
+                    help='with --dtype bf16 or --split_planes: time the float32 chain too')
+    ap.add_argument('--compare_all', action='store_true', help='alternate the fp32, bf16 and split-plane chains')
+    ap.add_argument('--rounds', type=int, default=3, help='alternations of the chains under --compare_fp32 / _all')
     ap.add_argument('--batch', type=int, default=4)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
@@ -130,12 +144,19 @@ def main():
     ap.add_argument('--no_library', action='store_true')
     ap.add_argument('--out', type=str, default=None)
     a = ap.parse_args()
+    if a.split_planes and a.dtype != 'fp32':
+        ap.error('--split_planes is the float32-accurate mode: it cannot be combined with --dtype %s' % a.dtype)
     if not torch.cuda.is_available():
         raise SystemExit('segnet_bench: no GPU (nothing is measured without one)')
     torch.cuda.set_device(0)
     p = random_params()
-    dtypes = [a.dtype] + (['fp32'] if a.compare_fp32 and a.dtype != 'fp32' else [])
-    models = {dt: segnet.SegNetBasic(p, pred_shape=(2 * a.H, 2 * a.W), dtype=dt) for dt in dtypes}
+    main_mode = 'f16x3' if a.split_planes else a.dtype
+    if a.compare_all:
+        dtypes = [main_mode] + [m for m in MODES if m != main_mode]
+    else:
+        dtypes = [main_mode] + (['fp32'] if a.compare_fp32 and main_mode != 'fp32' else [])
+    models = {m: segnet.SegNetBasic(p, pred_shape=(2 * a.H, 2 * a.W), dtype='bf16' if m == 'bf16' else 'fp32',
+                                    split_planes=m == 'f16x3') for m in dtypes}
     g = torch.Generator(device='cuda').manual_seed(1)
     x = torch.randint(0, 256, (a.batch, 3, a.H, a.W), generator=g, device='cuda').float()
     flops = {k: v * a.batch * (a.H * a.W) / (512.0 * 1024.0) for k, v in segnet.layer_flops().items()}
@@ -165,15 +186,18 @@ def main():
     for dt in dtypes:
         layers = {k: float(np.median([d[k] for d in per_layer[dt]])) for k in per_layer[dt][0]}
         out[dt] = report(dt, a, layers, float(np.median(per_chain[dt])), flops)
-    res = out[a.dtype]
-    if a.dtype == 'fp32':
+    res = out[main_mode]
+    if main_mode == 'fp32':
         res['peak_tflops_f32_matrix'] = PEAK_TF['fp32']
     if len(dtypes) > 1:
         res['rounds'] = a.rounds
-        res['chain_ms_rounds'] = per_chain[a.dtype]
-        res['fp32'] = out['fp32']
-        res['fp32']['chain_ms_rounds'] = per_chain['fp32']
-        res['chain_ratio_to_fp32'] = res['chain_ms'] / out['fp32']['chain_ms']
+        for dt in dtypes:
+            out[dt]['chain_ms_rounds'] = per_chain[dt]
+            if dt != 'fp32':
+                out[dt]['chain_ratio_to_fp32'] = out[dt]['chain_ms'] / out['fp32']['chain_ms']
+                out[dt]['chain_ratio_to_fp32_rounds'] = [m / f for m, f in zip(per_chain[dt], per_chain['fp32'])]
+            if dt != main_mode:
+                res[dt] = out[dt]
     if not a.no_library:
         for _ in range(a.warmup):
             library_forward(p, x, lambda n: None)

@@ -17,8 +17,9 @@ with the size of the (per-rank) training set.
 every 7x7 convolution pass of a training step on the bf16 matrix cores, with float32 accumulation, float32 master
 weights, BatchNorm and optimizer.  The dtype goes into args.txt and every snapshot.  --resume continues bit for bit in
 the snapshot's own dtype, and a float32 snapshot may also be resumed in bf16 or the other way round (the weights and the
-optimizer state are float32 in both).  Validation always runs the float32 inference network, and labels_from_segnet.py
-reads the snapshots of either dtype.
+optimizer state are float32 in both).  Validation runs the float32 inference network in every training mode unless
+--val_split_planes is given (its float32-accurate form on the f16 matrix cores, segnet.SegNetBasic split_planes;
+recorded in args.txt only when given), and labels_from_segnet.py reads the snapshots of either dtype.
 
 --split_planes (also parsed in front of the reference flags): run every 7x7 convolution pass of the float32 step at
 float32 accuracy on the f16 matrix cores (each operand as two power-of-two-scaled half-precision planes, three products
@@ -109,13 +110,16 @@ def get_dtype_args(argv=None):
 
 def get_pre_args(argv=None):
     """-> (namespace of this implementation's flags, the remaining arguments for get_args): --dtype (get_dtype_args),
-    --split_planes and --data_parallel, read by one pre-parser in front of the reference flag set of get_parser."""
+    --split_planes, --val_split_planes and --data_parallel, read by one pre-parser in front of the reference flag set of
+    get_parser."""
     argv = list(sys.argv[1:] if argv is None else argv)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'],
                      help='operands of the 7x7 convolution passes: float32 or bf16 (float32 accumulation)')
     pre.add_argument('--split_planes', action='store_true', default=False,
                      help='float32 step with its 7x7 passes at float32 accuracy on the f16 matrix cores')
+    pre.add_argument('--val_split_planes', action='store_true', default=False,
+                     help='validation passes at float32 accuracy on the f16 matrix cores (SegNetBasic split_planes)')
     pre.add_argument('--data_parallel', action='store_true', default=False,
                      help='run as one rank of a torchrun launch (RANK / WORLD_SIZE / LOCAL_RANK)')
     return pre.parse_known_args(argv)
@@ -130,13 +134,16 @@ def check_split_planes(pre):
 
 def run_args(argv=None):
     """-> (the pre-parser's namespace, the run's arguments as args.txt records them, before a data-parallel run adds
-    its world size): the reference flags plus dtype, and split_planes / data_parallel only where they are given."""
+    its world size): the reference flags plus dtype, and split_planes / val_split_planes / data_parallel only where they
+    are given."""
     pre, argv = get_pre_args(argv)
     check_split_planes(pre)
     args = get_args(argv)
     args.dtype = pre.dtype
     if pre.split_planes:
         args.split_planes = True                   # args.txt records it; a default run's args.txt is unchanged
+    if pre.val_split_planes:
+        args.val_split_planes = True               # likewise: recorded only when given
     if pre.data_parallel:
         args.data_parallel = True                  # args.txt records it with the world size; one-process runs unchanged
     return pre, args
@@ -177,12 +184,13 @@ def _iterations(interval, n_data, batchsize):
     raise ValueError('unknown interval unit %r' % unit)
 
 
-def evaluate(trainer, valid, eval_shape, batchsize, indices=None):
+def evaluate(trainer, valid, eval_shape, batchsize, indices=None, split_planes=False):
     """SemanticSegmentationEvaluator + PrecisionRecallEvaluator over the validation set (or its examples `indices`)
     with the inference network (BN folded from the running statistics), predicting as labels_from_segnet.py does ->
-    the report entries."""
+    the report entries.  split_planes: the predictor's float32-accurate convolutions on the f16 matrix cores
+    (--val_split_planes) instead of the float32 ones."""
     import torch
-    model = trainer.predictor(eval_shape)
+    model = trainer.predictor(eval_shape, split_planes=True) if split_planes else trainer.predictor(eval_shape)
     eng = trainer.eng
     in_shape = tuple(int(v) for v in valid.resize_shape)
     indices = list(range(len(valid))) if indices is None else [int(i) for i in indices]
@@ -322,7 +330,8 @@ def main(argv=None):
             opt.lr *= 0.1                                            # ExponentialShift('lr', 0.1)
         report = {}
         if iteration % val_every == 0:
-            report.update(evaluate(trainer, valid, args.eval_shape, args.batchsize, valid_ids))
+            report.update(evaluate(trainer, valid, args.eval_shape, args.batchsize, valid_ids,
+                                   split_planes=pre.val_split_planes))
             if group is not None:
                 report = group.mean_over_ranks(report)               # create_multi_node_evaluator: mean over ranks
         if iteration % log_every == 0:

@@ -30,7 +30,9 @@ Additions, defaulting to what the reference hard-codes: --input_shape, --val_img
 leaves in place; the driver's own --eval_shape is the labelling shape only), --dtype (the training rounds' dtype
 only), --label_dtype (the labelling passes' convolution precision, labels_from_segnet.py --dtype; fp32 unless given,
 whatever --dtype is), --split_planes (the training rounds' train_segnet.py --split_planes: float32 steps with their
-convolution passes on split f16 planes; passed to the training children only when given), --n_labels (overrides the
+convolution passes on split f16 planes; passed to the training children only when given), --label_split_planes (the
+labelling passes' labels_from_segnet.py --split_planes: float32-accurate inference on the f16 matrix cores;
+independent of --split_planes and --dtype, refused with --label_dtype bf16), --n_labels (overrides the
 split's constant), --no_figure (the labellers' 3-panel figures), --child_timeout.
 plan() computes the rounds, their commands, resume paths, result-directory prefixes and zip names without launching
 anything.
@@ -91,6 +93,8 @@ def get_parser():
                         help="labels_from_segnet.py's --dtype for the labelling passes (independent of --dtype)")
     parser.add_argument('--split_planes', action='store_true', default=False,
                         help="train_segnet.py --split_planes for the training rounds (float32 only)")
+    parser.add_argument('--label_split_planes', action='store_true', default=False,
+                        help="labels_from_segnet.py --split_planes for the labelling passes (--label_dtype fp32 only)")
     parser.add_argument('--n_labels', type=int, default=None, help='images to relabel (default: the split size)')
     parser.add_argument('--no_figure', action='store_true', default=False)
     parser.add_argument('--child_timeout', type=float, default=0,
@@ -103,6 +107,9 @@ def get_args(argv=None):
     args = parser.parse_args(argv)
     if args.split_planes and args.dtype != 'fp32':
         parser.error('--split_planes (float32 steps on split planes) does not combine with --dtype %s' % args.dtype)
+    if args.label_split_planes and args.label_dtype != 'fp32':
+        parser.error('--label_split_planes (float32-accurate labelling on split planes) does not combine with '
+                     '--label_dtype %s' % args.label_dtype)
     n_labels = args.n_labels
     if args.test_mode:
         args.iteration = 10
@@ -315,7 +322,8 @@ def label_worker(spec):
         save_labels(spec['param_dir'], spec['iteration'], spec['device'], spec['img_zip_fn'], spec['label_zip_fn'],
                     spec['out_dir'], spec['start'], spec['end'], spec['soft_label'], spec['eval_shape'],
                     spec['save_each'], figure=spec['figure'], result_fn=os.path.join(spool, 'result.json'),
-                    on_labels=None if spec['save_each'] else spool_one, dtype=spec['dtype'])
+                    on_labels=None if spec['save_each'] else spool_one,
+                    split_planes=spec.get('split_planes', False), dtype=spec['dtype'])
 
 
 def _child_main(target, arg, parent_pid):
@@ -395,6 +403,7 @@ def create_label_from_model(args, param_dir, iteration, out_dir, out_zip):
                       'img_zip_fn': args.img_zip_fn, 'label_zip_fn': args.label_zip_fn, 'out_dir': out_dir,
                       'start': start, 'end': end, 'soft_label': soft_label, 'eval_shape': list(args.eval_shape),
                       'save_each': args.save_each, 'figure': not args.no_figure, 'dtype': args.label_dtype,
+                      'split_planes': args.label_split_planes,
                       'spool': os.path.join(spool_root, 'w%d' % i)})
     run_workers(label_worker, specs, args.child_timeout)
     spools = [s['spool'] for s in specs]
