@@ -128,6 +128,8 @@ struct spa_ctx {
     int ws_generation;             // counts workspace re-allocations (spa_ws_generation: captured graphs hold workspace addresses)
     int dbg_slic_ldsx;             // spa_debug_set key 2 (diagnostic builds: the reproducer variant of k_slic_assign)
     int convp_on;                  // spa_debug_set key 1 (spa_convp.hip instead of spa_conv32.hip's narrow tiles)
+    int convs2_on;                 // spa_debug_set key 3 (spa_convs2.hip's 2-D tile kernel for the stride-2 openers)
+    int convs2_attr_done;
     int rs_key[4], rs_ks[2];       // bicubic tables held in WS_RESIZE_TAB: (H, W, h, w) and tap counts
 };
 

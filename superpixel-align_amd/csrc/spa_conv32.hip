@@ -539,6 +539,11 @@ extern "C" int spa_conv1x1_f16s(spa_ctx *ctx, const float *x, int32_t B, int32_t
                               0, 0, 0, amax_in, amax_out, inv_t);
 }
 
+bool conv3x3_s2_tile_takes(int32_t Cin, int32_t Cout, int32_t csplit, const float *y2);                      // spa_convs2.hip
+int conv3x3_s2_tile_launch(spa_ctx *ctx, const float *x, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, const void *wt2, float inv_t,
+                           int32_t csplit, const float *bias, int32_t relu, const void *amax_in, void *amax_out, float *y, float *y2,
+                           hipStream_t s);
+
 // 3x3 stride-2 padding-1 convolution (the first convolution of layers 3 and 4, models/drn.py:204-206) on the 16-bit matrix
 // cores at float32 accuracy, optionally together with the block's 1x1 stride-2 projection as output channels
 // [csplit, Cout) (wt2 rows csplit.. hold the projection's weights at the centre tap, zeros elsewhere): one pass over the
@@ -560,6 +565,12 @@ extern "C" int spa_conv3x3_s2_f16s(spa_ctx *ctx, const float *x, int32_t B, int3
         ctx->zero_line_ready = 1;
     }
     if (amax_out) spa_zero_word(amax_out, s);
+    // round 7: the networks' shapes take the 2-D tile kernel of spa_convs2.hip (bit-identical outputs; spa_debug_set(ctx, 3, 0): this
+    // file's kernel for every shape, kept for A/B runs and for the shapes that kernel does not take)
+    if (ctx->convs2_on && conv3x3_s2_tile_takes(Cin, Cout, csplit, y2)) {
+        SpaProfScope prof_(ctx, PROF_DRN_CONV16_FRONT, s);
+        return conv3x3_s2_tile_launch(ctx, x, B, Hi, Wi, Cin, wt2, inv_t, csplit, bias, relu, amax_in, amax_out, y, y2, s);
+    }
     const int H = (Hi + 1) / 2, W = (Wi + 1) / 2;
     // (64-pixel tiles, two workgroups per CU for the 128-row form, were measured: 2.06 vs 1.95 ms on the 32 -> 64+64 layer)
     const int bm = Cout % 256 == 0 ? 256 : 128, bn = 128;

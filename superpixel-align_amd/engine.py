@@ -122,7 +122,8 @@ class Engine(object):
 
     def debug_set(self, key, value):
         """diagnostic kernel-selection switches (include/spalign.h: spa_debug_set); key 1 = planes-in-LDS kernel for the narrow
-        split-plane 3x3 layers (1, default) or the kernel it replaced (0)"""
+        split-plane 3x3 layers (1, default) or the kernel it replaced (0); key 3 = the 2-D tile kernel for the stride-2 openers
+        (conv3x3_s2_f16s; 1, default) or the generic kernel for every shape (0)"""
         check(self._lib.spa_debug_set(self._ctx, int(key), int(value)))
 
     # ------------------------------------------------------------------ per-kernel timing
