@@ -555,6 +555,31 @@ int spa_segnet_decode_f16x3(spa_ctx *ctx, const float *x, const uint8_t *idx, in
 int spa_segnet_score(spa_ctx *ctx, const float *prob, int32_t B, int32_t h, int32_t w, int32_t H, int32_t W,
                      uint8_t *mask, float *scores, void *stream);
 
+/* ---- SegNet-Basic training input stage (train_segnet.py --loader_procs; csrc/spa_segnet_input.hip) --------------
+ * What segnet_train.ZippedEstimatedCityscapesDataset.get_example computes on the host from a decoded frame, with
+ * the same bits.  src (B,H,W,3) uint8 interleaved -> out (B,3,h,w) float32 planar, 0..255 (not standardised): each
+ * channel widened to float32 and resized as a FLOAT image, then shift[b*3+c] (doubles, NULL: none) added as
+ * (float)((double)v + shift) (numpy's float32 += float64), then the rows mirrored where flip[b] != 0 (NULL: none).
+ * H == h and W == w: no resize.  backend 0, Pillow's mode 'F' BICUBIC: xb (w,2) int32 {first tap, tap count}, xk
+ * (w,ksx) normalised float64 taps (segnet_train.pil_bicubic_coeffs), yb / yk (h,..) likewise; per output sample a
+ * double starting at 0 accumulates (double)v * k in tap order (two roundings per tap) and is stored as float32, the
+ * horizontal pass first, the vertical pass over its float32 results, and a pass whose size does not change is not run
+ * (its tables may be NULL).  backend 1, OpenCV's float INTER_CUBIC as segnet_train.resize_bicubic_float restates it:
+ * xb (w,4) clamped source indices, xk (w,4) float32 taps, a float32 sum from 0 of float32 products in tap order, both
+ * passes always.  tmp: (B,3,H,w) float32 scratch, needed when both passes run.  All tables are device pointers whose
+ * indices the caller has checked against (H, W).  No atomics, no host synchronisation. */
+int spa_segnet_train_input(spa_ctx *ctx, const uint8_t *src, int32_t B, int32_t H, int32_t W, int32_t h, int32_t w,
+                           int32_t backend, const int32_t *xb, const void *xk, int32_t ksx, const int32_t *yb,
+                           const void *yk, int32_t ksy, const double *shift, const uint8_t *flip, float *tmp,
+                           float *out, void *stream);
+/* The labels of the same examples: out[b,c,y,x'] = src[b,c,yi[y],xi[x]], x' = w-1-x where flip[b] != 0 (NULL: none).
+ * is_float 0: src uint8 (B,C,H,W) masks -> out int32; 1: src float32 scores -> out float32.  yi (h), xi (w): the
+ * source index of every output row / column (segnet_train.nearest_index_table: Pillow's NEAREST or cv.INTER_NEAREST),
+ * device pointers whose values the caller has checked against (H, W). */
+int spa_segnet_train_label(spa_ctx *ctx, const void *src, int32_t is_float, int32_t B, int32_t C, int32_t H, int32_t W,
+                           int32_t h, int32_t w, const int32_t *yi, const int32_t *xi, const uint8_t *flip, void *out,
+                           void *stream);
+
 /* ---- SegNet-Basic training (train_segnet.py --model basic) ----------------------------------------------------
  * The 7x7 convolutions (padding 3, stride 1, no bias) of the training step on the float32 matrix cores; BatchNorm,
  * ReLU, pooling and the loss are the caller's.  (H, W) is the convolution's resolution: multiples of 16 for conv1

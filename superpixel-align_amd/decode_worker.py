@@ -57,6 +57,46 @@ def decode_into(task):
     return tuple(a.shape)
 
 
+def label_into(task):
+    """(shm name, byte offset, expected shape, (zip path, member name)) -> (shape, dtype string) of the .npy member
+    of an npz-style label zip (cli.write_label_zip, run_train_rounds.py): a 2-D road mask of bool or uint8, or a
+    float32 (C,H,W) score map.  Its bytes are read straight into the slab at the offset when it is C-ordered, of
+    one of those dtypes and of the expected shape; the caller falls back otherwise."""
+    from numpy.lib import format as npf
+    name, offset, shape, src = task
+    with _open(src) as fp:
+        version = npf.read_magic(fp)
+        head = npf.read_array_header_1_0 if version == (1, 0) else npf.read_array_header_2_0
+        a_shape, fortran, dtype = head(fp)
+        ok = not fortran and tuple(a_shape) == tuple(shape) and (
+            (len(a_shape) == 2 and dtype in (np.dtype(np.bool_), np.dtype(np.uint8)))
+            or (len(a_shape) == 3 and dtype == np.dtype('<f4')))
+        if ok:
+            n = int(np.prod(a_shape)) * dtype.itemsize
+            dst = memoryview(_attach(name).buf)[offset:offset + n]
+            got = 0
+            while got < n:
+                k = fp.readinto(dst[got:])
+                if not k:
+                    raise EOFError('%s: %d of %d bytes' % (src[1], got, n))
+                got += k
+            dst.release()
+    return tuple(a_shape), dtype.str
+
+
+def die_with_parent(parent_pid):
+    """initializer of a pool whose workers must not outlive the process that made it: SIGTERM once the parent is gone
+    (Linux PR_SET_PDEATHSIG), and at once if it already is (utils/run_train_rounds.py gives its children the same)"""
+    import ctypes
+    import signal
+    try:
+        ctypes.CDLL(None, use_errno=True).prctl(1, int(signal.SIGTERM), 0, 0, 0)      # PR_SET_PDEATHSIG = 1
+    except (OSError, AttributeError):
+        return
+    if os.getppid() != parent_pid:
+        os.kill(os.getpid(), signal.SIGTERM)
+
+
 def warm(_):
     """first task of every worker: import Pillow's PNG plugin now, not inside the first batch"""
     from PIL import Image, PngImagePlugin  # noqa: F401

@@ -57,6 +57,7 @@ class Engine(object):
         h = ctypes.c_void_p()
         check(self._lib.spa_ctx_create(self.device.index, ctypes.byref(h)))
         self._ctx = h
+        self._in_tables = {}           # segnet_train_input / _label: device tables per (kind, n_in, n_out, backend)
 
     def _s(self):
         """The launch stream: torch's current stream of THIS engine's device (a spa_ctx is bound to one
@@ -891,6 +892,99 @@ class Engine(object):
         sc = torch.empty((B, 2, H, W), dtype=torch.float32, device=prob.device) if want_scores else None
         check(self._lib.spa_segnet_score(self._ctx, _ptr(prob), B, h, w, H, W, _ptr(mask), _ptr(sc), self._s()))
         return mask, sc
+
+    # ---- SegNet-Basic training input stage (segnet_loader.py): get_example's arithmetic on decoded batches
+    def _input_tables(self, kind, n_in, n_out, backend):
+        """Device tables of one axis, uploaded once per (kind, n_in, n_out, backend): 'cubic' -> (bounds, taps, ksize)
+        of segnet_train.pil_bicubic_coeffs or _cv_cubic_float_taps, 'nearest' -> segnet_train.nearest_index_table."""
+        from . import segnet_train as st
+        cache = self._in_tables
+        key = (kind, int(n_in), int(n_out), backend)
+        if key not in cache:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            if kind == 'nearest':
+                cache[key] = up(st.nearest_index_table(n_in, n_out, backend))
+            elif backend == 'cv2':
+                idx, taps = st._cv_cubic_float_taps(n_in, n_out)
+                assert ((idx >= 0) & (idx < n_in)).all()
+                cache[key] = (up(idx.astype(np.int32)), up(taps.astype(np.float32)), 4)
+            else:
+                bounds, taps = st.pil_bicubic_coeffs(n_in, n_out)
+                cache[key] = (up(bounds), up(taps), int(taps.shape[1]))
+        return cache[key]
+
+    @staticmethod
+    def _input_backend(backend):
+        if backend is None:
+            from . import cli
+            backend = cli.RESIZE_BACKEND[0]
+        if backend not in ('pil', 'cv2'):
+            raise SpalignError("resize backend must be 'pil' or 'cv2', got %r" % (backend,))
+        return backend
+
+    def _flip(self, flip, B):
+        if flip is None:
+            return None
+        flip = _req(flip, torch.uint8, 'flip')
+        if tuple(flip.shape) != (B,):
+            raise SpalignError('flip must be (B,) uint8, got %s' % (tuple(flip.shape),))
+        return flip
+
+    def segnet_train_input(self, src, shape, shift=None, flip=None, backend=None):
+        """Decoded frames (B,H,W,3) uint8 -> the training images (B,3,h,w) float32 0..255 with the bits of
+        ZippedEstimatedCityscapesDataset.get_example: each channel resized as a float image (Pillow's mode 'F' BICUBIC,
+        or with backend 'cv2' resize_bicubic_float's OpenCV form; backend None: cli.RESIZE_BACKEND), then shift (B,3)
+        float64 (pca_lighting_shift of each image's draw) added as numpy's float32 += float64, then the images with
+        flip (B,) uint8 != 0 mirrored.  Equal sizes: widened only."""
+        src = _req(src, torch.uint8, 'src')
+        if src.dim() != 4 or src.shape[3] != 3:
+            raise SpalignError('segnet_train_input: src must be (B,H,W,3) uint8, got %s' % (tuple(src.shape),))
+        B, H, W, _ = src.shape
+        h, w = int(shape[0]), int(shape[1])
+        backend = self._input_backend(backend)
+        if shift is not None:
+            shift = _req(shift, torch.float64, 'shift')
+            if tuple(shift.shape) != (B, 3):
+                raise SpalignError('shift must be (B,3) float64, got %s' % (tuple(shift.shape),))
+        flip = self._flip(flip, B)
+        out = torch.empty((B, 3, h, w), dtype=torch.float32, device=src.device)
+        xb = xk = yb = yk = tmp = None
+        ksx = ksy = 0
+        if (H, W) != (h, w):
+            cv = backend == 'cv2'
+            if cv or W != w:
+                xb, xk, ksx = self._input_tables('cubic', W, w, backend)
+            if cv or H != h:
+                yb, yk, ksy = self._input_tables('cubic', H, h, backend)
+            if xb is not None and yb is not None:
+                tmp = torch.empty((B, 3, H, w), dtype=torch.float32, device=src.device)
+        check(self._lib.spa_segnet_train_input(self._ctx, _ptr(src), B, H, W, h, w, 1 if backend == 'cv2' else 0,
+                                               _ptr(xb), _ptr(xk), ksx, _ptr(yb), _ptr(yk), ksy, _ptr(shift),
+                                               _ptr(flip), _ptr(tmp), _ptr(out), self._s()))
+        return out
+
+    def segnet_train_label(self, src, shape, flip=None, backend=None):
+        """The labels of the same examples: uint8 masks (B,H,W) -> int32 (B,h,w), or float32 scores (B,C,H,W) ->
+        float32 (B,C,h,w), resized as resize_nearest_label does (Pillow's NEAREST, or cli.resize_nearest with backend
+        'cv2') and mirrored where flip (B,) uint8 != 0."""
+        if src.dtype == torch.uint8 and src.dim() == 3:
+            src = _req(src, torch.uint8, 'src')
+            is_float, C, out_dtype = 0, 1, torch.int32
+        elif src.dtype == torch.float32 and src.dim() == 4:
+            src = _req(src, torch.float32, 'src')
+            is_float, C, out_dtype = 1, int(src.shape[1]), torch.float32
+        else:
+            raise SpalignError('segnet_train_label: src must be (B,H,W) uint8 or (B,C,H,W) float32')
+        B, (H, W) = src.shape[0], src.shape[-2:]
+        h, w = int(shape[0]), int(shape[1])
+        backend = self._input_backend(backend)
+        flip = self._flip(flip, B)
+        yi = self._input_tables('nearest', H, h, backend)
+        xi = self._input_tables('nearest', W, w, backend)
+        out = torch.empty(tuple(src.shape[:-2]) + (h, w), dtype=out_dtype, device=src.device)
+        check(self._lib.spa_segnet_train_label(self._ctx, _ptr(src), is_float, B, C, H, W, h, w, _ptr(yi), _ptr(xi),
+                                               _ptr(flip), _ptr(out), self._s()))
+        return out
 
     # ---- SegNet-Basic training (segnet_train.py).  Maps are (B,H,W,64) contiguous tensors (channels-last storage);
     # conv1's input is the planar (B,3,H,W) float32 image 0..255.

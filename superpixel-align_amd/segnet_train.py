@@ -556,10 +556,11 @@ def shard_indices(n, n_ranks, rank, shuffle=True, seed=0):
 DP_KEY = 'extensions/data_parallel/'      # data-parallel snapshots: world size, every rank's iterator and numpy state
 
 
-def rank_state(iterator):
-    """this rank's iterator state and numpy random state, as a data-parallel snapshot stores them per rank"""
-    st = np.random.get_state()
-    out = {'iterator/' + k: np.asarray(v) for k, v in iterator.state().items()}
+def rank_state(iterator, state=None):
+    """this rank's iterator state and numpy random state, as a data-parallel snapshot stores them per rank.  state:
+    the (iterator state, numpy state) pair a TrainLoader captured with the batch, instead of the live ones."""
+    it_state, st = state if state is not None else (iterator.state(), np.random.get_state())
+    out = {'iterator/' + k: np.asarray(v) for k, v in it_state.items()}
     out.update({'np_random/keys': st[1], 'np_random/pos': np.asarray(st[2]), 'np_random/has_gauss': np.asarray(st[3]),
                 'np_random/cached_gaussian': np.asarray(st[4])})
     return out
@@ -594,11 +595,12 @@ def load_rank_state(path, rank):
 OPT = 'updater/optimizer:main/'
 
 
-def save_snapshot(path, trainer, iteration, lr, iterator_state, extra=None):
+def save_snapshot(path, trainer, iteration, lr, iterator_state, extra=None, np_state=None):
     """A Chainer-style npz: updater/model:main/predictor/<link>/<param> (what segnet.load_snapshot reads), the
     optimizer state under updater/optimizer:main/predictor/<link>/<param>/<state>, the iteration, lr, the iterator,
     numpy's random state (so --resume continues bit for bit), under DTYPE_KEY the trainer's dtype and, for a
-    split-plane trainer only, SPLIT_PLANES_KEY = True."""
+    split-plane trainer only, SPLIT_PLANES_KEY = True.  np_state: the numpy state to store instead of the live one
+    (the one a TrainLoader captured with the batch of this iteration)."""
     d = {}
     for k, v in trainer.params_numpy().items():
         d[segnet.PREFIX + k] = v
@@ -611,7 +613,7 @@ def save_snapshot(path, trainer, iteration, lr, iterator_state, extra=None):
     d['updater/iteration'] = np.asarray(iteration)
     for k, v in iterator_state.items():
         d['updater/iterator:main/' + k] = np.asarray(v)
-    st = np.random.get_state()
+    st = np.random.get_state() if np_state is None else np_state
     d['extensions/np_random/keys'] = st[1]
     d['extensions/np_random/pos'] = np.asarray(st[2])
     d['extensions/np_random/has_gauss'] = np.asarray(st[3])
@@ -666,16 +668,94 @@ def load_snapshot_state(path):
 
 
 # ------------------------------------------------------------------------------- dataset
+def pca_lighting_shift(alpha):
+    """The three float64 channel shifts pca_lighting adds for the drawn alpha (3,)."""
+    eigen_value = np.array((0.2175, 0.0188, 0.0045))
+    eigen_vector = np.array(((-0.5675, -0.5808, -0.5836), (0.7192, -0.0045, -0.6948), (0.4009, -0.8140, 0.4203)))
+    return eigen_vector.dot(eigen_value * alpha)
+
+
 def pca_lighting(img, sigma):
     """chainercv.transforms.pca_lighting(img, sigma) with its default eigen decomposition, numpy's global stream."""
     if sigma <= 0:
         return img
-    eigen_value = np.array((0.2175, 0.0188, 0.0045))
-    eigen_vector = np.array(((-0.5675, -0.5808, -0.5836), (0.7192, -0.0045, -0.6948), (0.4009, -0.8140, 0.4203)))
     alpha = np.random.normal(0, sigma, size=3)
     img = img.copy()
-    img += eigen_vector.dot(eigen_value * alpha).reshape((-1, 1, 1))
+    img += pca_lighting_shift(alpha).reshape((-1, 1, 1))
     return img
+
+
+def pil_bicubic_coeffs(n_in, n_out):
+    """Pillow's precompute_coeffs (src/libImaging/Resample.c) for BICUBIC (a = -0.5) along one axis, in float64 with
+    its operation order -> (bounds (n_out, 2) int32 {first tap, tap count}, taps (n_out, ksize) float64 normalised by
+    their sequential sum, unused entries 0).  The tables of a mode 'F' resize, which applies them unrounded
+    (Engine.segnet_train_input, pil_resize_float)."""
+    scale = float(n_in) / float(n_out)
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    ksize = int(np.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), n_in) - xmin
+    a = -0.5
+    k = np.zeros((n_out, ksize), np.float64)
+    ww = np.zeros(n_out, np.float64)
+    for x in range(ksize):
+        t = np.abs((x + xmin - center + 0.5) * ss)
+        near = ((a + 2.0) * t - (a + 3.0)) * t * t + 1
+        far = (((t - 5) * t + 8) * t - 4) * a
+        wgt = np.where(x < xmax, np.where(t < 1.0, near, np.where(t < 2.0, far, 0.0)), 0.0)
+        k[:, x] = wgt
+        ww = ww + wgt                                # tap order; the zeros past a row's count change nothing
+    nz = ww != 0.0
+    k[nz] = k[nz] / ww[nz, None]
+    assert ((xmin >= 0) & (xmax >= 0) & (xmin + xmax <= n_in) & (xmax <= ksize)).all()
+    return np.stack([xmin, xmax], 1).astype(np.int32), k
+
+
+def pil_resize_float(img, shape):
+    """Pillow's mode 'F' BICUBIC resize of a float32 (C,H,W) image restated in numpy: per output sample a float64 that
+    starts at 0 accumulates float64(v) * k in tap order and is stored as float32, the horizontal pass first, the
+    vertical pass over its float32 results; a pass whose size does not change is not run.  The arithmetic of
+    csrc/spa_segnet_input.hip; equal to resize_bicubic_float's Pillow branch bit for bit."""
+    h, w = int(shape[0]), int(shape[1])
+    img = np.asarray(img, np.float32)
+    if img.shape[2] != w:
+        b, k = pil_bicubic_coeffs(img.shape[2], w)
+        acc = np.zeros(img.shape[:2] + (w,), np.float64)
+        for t in range(k.shape[1]):
+            idx = np.minimum(b[:, 0] + t, img.shape[2] - 1)
+            term = img[:, :, idx].astype(np.float64) * k[None, None, :, t]
+            acc = np.where(t < b[None, None, :, 1], acc + term, acc)
+        img = acc.astype(np.float32)
+    if img.shape[1] != h:
+        b, k = pil_bicubic_coeffs(img.shape[1], h)
+        acc = np.zeros((img.shape[0], h, img.shape[2]), np.float64)
+        for t in range(k.shape[1]):
+            idx = np.minimum(b[:, 0] + t, img.shape[1] - 1)
+            term = img[:, idx, :].astype(np.float64) * k[None, :, t, None]
+            acc = np.where(t < b[None, :, 1, None], acc + term, acc)
+        img = acc.astype(np.float32)
+    return img
+
+
+def nearest_index_table(n_src, n_dst, backend='pil'):
+    """The source index of every destination index under resize_nearest_label -> (n_dst,) int32.  'pil': Pillow's
+    NEAREST of Image.resize (an affine scale: the source coordinate starts at half a step and grows by repeated
+    float64 addition of n_src / n_dst, truncated); 'cv2': cli.nearest_index."""
+    if backend == 'cv2':
+        from . import cli
+        out = cli.nearest_index(n_dst, n_src).astype(np.int32)
+    else:
+        step = float(n_src) / float(n_dst)
+        out = np.empty(n_dst, np.int32)
+        xo = step * 0.5
+        for x in range(n_dst):
+            out[x] = int(xo)
+            xo += step
+    assert ((out >= 0) & (out < n_src)).all()
+    return out
 
 
 def _cv_cubic_float_taps(n_src, n_dst):
@@ -757,7 +837,8 @@ class ZippedEstimatedCityscapesDataset(object):
     def __len__(self):
         return len(self.img_fns)
 
-    def get_example(self, i):
+    def decoded(self, i):
+        """-> (the decoded float32 (3,H,W) image, the label member as int32 (H,W) or float32 (2,H,W)), full size"""
         from PIL import Image
         if self.img_zf is None:
             self.img_zf = zipfile.ZipFile(self.img_zip_fn)
@@ -767,17 +848,37 @@ class ZippedEstimatedCityscapesDataset(object):
             img = np.asarray(f.convert('RGB'), dtype=np.float32).transpose(2, 0, 1)
         label = self.label_zf[self.label_fns[i][:-len('.npy')]]
         label = label.astype(np.float32) if self.use_soft_label else label.astype(np.int32)
+        return img, label
+
+    def get_example(self, i):
+        img, label = self.resized(*self.decoded(i))
+        if self.random:
+            img = pca_lighting(img, 25.5)
+            if np.random.rand() > 0.5:
+                img = img[:, :, ::-1]
+                label = label[..., ::-1]
+        return np.ascontiguousarray(img, np.float32), np.ascontiguousarray(label)
+
+    def resized(self, img, label):
+        """get_example's resize of a decoded float32 (3,H,W) image and its converted label, each only where its size
+        is not resize_shape"""
         if img.shape[1:] != self.resize_shape:
             img = resize_bicubic_float(img, self.resize_shape)
         if label.shape[-2:] != self.resize_shape:
             label = resize_nearest_label(label if self.use_soft_label else label[None], self.resize_shape)
             if not self.use_soft_label:
                 label = label[0]
-        if self.random:
-            img = pca_lighting(img, 25.5)
-            if np.random.rand() > 0.5:
-                img = img[:, :, ::-1]
-                label = label[..., ::-1]
+        return img, label
+
+    @staticmethod
+    def augmented(img, label, shift, flip):
+        """get_example's --random part with the draws made by the caller (segnet_loader.TrainLoader): shift =
+        pca_lighting_shift(np.random.normal(0, 25.5, 3)), flip = np.random.rand() > 0.5, drawn in that order."""
+        img = img.copy()
+        img += np.asarray(shift, np.float64).reshape((-1, 1, 1))
+        if flip:
+            img = img[:, :, ::-1]
+            label = label[..., ::-1]
         return np.ascontiguousarray(img, np.float32), np.ascontiguousarray(label)
 
     @staticmethod

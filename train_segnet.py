@@ -35,6 +35,16 @@ scatter_dataset with shuffle), the validation set into contiguous shards, and ev
 mean of the ranks' values.  Only rank 0 writes args.txt (with data_parallel and world_size), the log (main/loss is its
 own) and the snapshots, which add the world size and every rank's iterator and numpy state; --resume continues bit
 for bit with the same world size and refuses another one.  One rank computes the one-process run's bits.
+
+--loader_procs N (also parsed in front of the reference flags; default 0: the loop decodes, resizes and augments every
+batch itself, one image after the other, between two steps).  With N > 0, N worker processes decode the PNGs and read
+the labels a few batches ahead into pinned shared-memory slabs, and the GPU resizes and augments them on a side stream
+(superpixel-align_amd/segnet_loader.py).  The run computes the bits of the default run: the same losses, the same
+snapshots (they store the iterator and numpy state that belong to their iteration, not the prefetching loader's), and
+--resume continues bit for bit from either kind of run with or without the flag.  args.txt records loader_procs only
+when it is given.  Under --data_parallel every rank has its own N workers: keep ranks x N within the CPUs the job has.
+A batch whose frames are not of the first frame's size takes the host path, and so does the whole run (it says so
+once) where /dev/shm cannot hold the slabs.
 """
 import argparse
 import importlib
@@ -110,8 +120,8 @@ def get_dtype_args(argv=None):
 
 def get_pre_args(argv=None):
     """-> (namespace of this implementation's flags, the remaining arguments for get_args): --dtype (get_dtype_args),
-    --split_planes, --val_split_planes and --data_parallel, read by one pre-parser in front of the reference flag set of
-    get_parser."""
+    --split_planes, --val_split_planes, --data_parallel and --loader_procs, read by one pre-parser in front of the
+    reference flag set of get_parser."""
     argv = list(sys.argv[1:] if argv is None else argv)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'],
@@ -122,6 +132,8 @@ def get_pre_args(argv=None):
                      help='validation passes at float32 accuracy on the f16 matrix cores (SegNetBasic split_planes)')
     pre.add_argument('--data_parallel', action='store_true', default=False,
                      help='run as one rank of a torchrun launch (RANK / WORLD_SIZE / LOCAL_RANK)')
+    pre.add_argument('--loader_procs', type=int, default=0,
+                     help='decode worker processes of the input stage (per rank); 0: the loop prepares its batches itself')
     return pre.parse_known_args(argv)
 
 
@@ -134,8 +146,8 @@ def check_split_planes(pre):
 
 def run_args(argv=None):
     """-> (the pre-parser's namespace, the run's arguments as args.txt records them, before a data-parallel run adds
-    its world size): the reference flags plus dtype, and split_planes / val_split_planes / data_parallel only where they
-    are given."""
+    its world size): the reference flags plus dtype, and split_planes / val_split_planes / data_parallel /
+    loader_procs only where they are given."""
     pre, argv = get_pre_args(argv)
     check_split_planes(pre)
     args = get_args(argv)
@@ -146,6 +158,10 @@ def run_args(argv=None):
         args.val_split_planes = True               # likewise: recorded only when given
     if pre.data_parallel:
         args.data_parallel = True                  # args.txt records it with the world size; one-process runs unchanged
+    if pre.loader_procs < 0:
+        raise ValueError('--loader_procs must be >= 0, got %d' % pre.loader_procs)
+    if pre.loader_procs:
+        args.loader_procs = pre.loader_procs       # recorded only when given
     return pre, args
 
 
@@ -222,6 +238,18 @@ def resume_check(snapshot_world_size, world_size):
         raise RuntimeError('--resume: the snapshot was written by %s, this run has %d rank(s); resume with the world '
                            'size that wrote it' % ('%d rank(s)' % snapshot_world_size if snapshot_world_size
                                                    else 'one process', world_size))
+
+
+def open_loader(n_procs, train, train_ids, it, stage):
+    """-> the run's segnet_loader.TrainLoader on n_procs workers, or None where /dev/shm cannot hold its slabs: the
+    run says so once and prepares its batches itself (nothing has been drawn, so the bits are the same)."""
+    sl = importlib.import_module('superpixel-align_amd.segnet_loader')
+    cli = importlib.import_module('superpixel-align_amd.cli')
+    try:
+        return sl.TrainLoader(train, train_ids, it, n_procs, stage)
+    except cli.ShmTooSmall as e:
+        print('--loader_procs: %s; the batches are prepared on the host' % e, flush=True)
+        return None
 
 
 def main(argv=None):
@@ -316,44 +344,59 @@ def main(argv=None):
     val_every = _iterations(args.val_interval, len(train_ids), args.batchsize)
     decay = args.decay_iteration if args.optimizer == 'MomentumSGD' else 0
     dev = trainer.eng.device
-    losses = []
-    t0 = time.time()
-    while iteration < stop:
-        ids = train_ids[it.next_indices()]
-        batch = [train.get_example(i) for i in ids]
-        img = torch.from_numpy(np.stack([b[0] for b in batch])).to(dev)
-        lab = torch.from_numpy(np.stack([b[1] for b in batch])).to(dev)
-        losses.append(trainer.step(img, lab))
-        lr_used = opt.lr                                             # observe_lr: Adam's is alpha_t of this step
-        iteration += 1
-        if decay > 0 and iteration % decay == 0:
-            opt.lr *= 0.1                                            # ExponentialShift('lr', 0.1)
-        report = {}
-        if iteration % val_every == 0:
-            report.update(evaluate(trainer, valid, args.eval_shape, args.batchsize, valid_ids,
-                                   split_planes=pre.val_split_planes))
-            if group is not None:
-                report = group.mean_over_ranks(report)               # create_multi_node_evaluator: mean over ranks
-        if iteration % log_every == 0:
-            entry = {'epoch': it.epoch, 'iteration': iteration, 'main/loss': float(np.mean(losses)),
-                     'lr': lr_used, 'elapsed_time': time.time() - t0}
-            entry.update(report)
-            losses = []
-            if rank == 0:
-                log.append(entry)
-                with open(os.path.join(result_dir, 'log'), 'w') as fp:
-                    json.dump(log, fp, indent=4)
-                print(json.dumps({k: entry.get(k) for k in ('iteration', 'main/loss', 'val/main/iou/road',
-                                                            'val_/main/precision', 'val_/main/recall', 'lr',
-                                                            'elapsed_time')}))
-        if iteration % val_every == 0:
-            extra = None
-            if dp:
-                states = group.gather_objects(st.rank_state(it)) if group is not None else [st.rank_state(it)]
-                extra = st.data_parallel_extra(states)
-            if rank == 0:
-                st.save_snapshot(os.path.join(result_dir, 'snapshot_iter_{}'.format(iteration)), trainer, iteration,
-                                 opt.lr, it.state(), extra)
+    loader = None
+    if pre.loader_procs:                           # after --resume has set the iterator and numpy's state
+        sl = importlib.import_module('superpixel-align_amd.segnet_loader')
+        loader = open_loader(pre.loader_procs, train, train_ids, it, sl.DeviceStage(train, trainer.eng))
+    # loader None: every batch is prepared here; else loader.next() hands out the same batches, each with the (iterator
+    # state, numpy state) the plain loop has after it, which the log and the snapshots then use
+    try:
+        losses = []
+        t0 = time.time()
+        while iteration < stop:
+            if loader is None:
+                ids = train_ids[it.next_indices()]
+                batch = [train.get_example(i) for i in ids]
+                img = torch.from_numpy(np.stack([b[0] for b in batch])).to(dev)
+                lab = torch.from_numpy(np.stack([b[1] for b in batch])).to(dev)
+                it_state, np_state = it.state(), None                    # the live states are this iteration's
+            else:
+                img, lab, (it_state, np_state) = loader.next()
+            losses.append(trainer.step(img, lab))
+            lr_used = opt.lr                                             # observe_lr: Adam's is alpha_t of this step
+            iteration += 1
+            if decay > 0 and iteration % decay == 0:
+                opt.lr *= 0.1                                            # ExponentialShift('lr', 0.1)
+            report = {}
+            if iteration % val_every == 0:
+                report.update(evaluate(trainer, valid, args.eval_shape, args.batchsize, valid_ids,
+                                       split_planes=pre.val_split_planes))
+                if group is not None:
+                    report = group.mean_over_ranks(report)               # create_multi_node_evaluator: mean over ranks
+            if iteration % log_every == 0:
+                entry = {'epoch': int(it_state['epoch']), 'iteration': iteration, 'main/loss': float(np.mean(losses)),
+                         'lr': lr_used, 'elapsed_time': time.time() - t0}
+                entry.update(report)
+                losses = []
+                if rank == 0:
+                    log.append(entry)
+                    with open(os.path.join(result_dir, 'log'), 'w') as fp:
+                        json.dump(log, fp, indent=4)
+                    print(json.dumps({k: entry.get(k) for k in ('iteration', 'main/loss', 'val/main/iou/road',
+                                                                'val_/main/precision', 'val_/main/recall', 'lr',
+                                                                'elapsed_time')}))
+            if iteration % val_every == 0:
+                extra = None
+                if dp:
+                    mine = st.rank_state(it, None if np_state is None else (it_state, np_state))
+                    states = group.gather_objects(mine) if group is not None else [mine]
+                    extra = st.data_parallel_extra(states)
+                if rank == 0:
+                    st.save_snapshot(os.path.join(result_dir, 'snapshot_iter_{}'.format(iteration)), trainer, iteration,
+                                     opt.lr, it_state, extra, np_state)
+    finally:
+        if loader is not None:
+            loader.close()
     if group is not None:
         group.barrier()                            # no rank leaves before rank 0's last snapshot is written
     return result_dir

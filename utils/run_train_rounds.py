@@ -32,7 +32,9 @@ only), --label_dtype (the labelling passes' convolution precision, labels_from_s
 whatever --dtype is), --split_planes (the training rounds' train_segnet.py --split_planes: float32 steps with their
 convolution passes on split f16 planes; passed to the training children only when given), --label_split_planes (the
 labelling passes' labels_from_segnet.py --split_planes: float32-accurate inference on the f16 matrix cores;
-independent of --split_planes and --dtype, refused with --label_dtype bf16), --n_labels (overrides the
+independent of --split_planes and --dtype, refused with --label_dtype bf16), --loader_procs (the training rounds'
+train_segnet.py --loader_procs: decode workers per rank and the input stage on the GPU, passed only when given; the
+job needs n_gpus x loader_procs CPUs for them), --n_labels (overrides the
 split's constant), --no_figure (the labellers' 3-panel figures), --child_timeout.
 plan() computes the rounds, their commands, resume paths, result-directory prefixes and zip names without launching
 anything.
@@ -95,6 +97,9 @@ def get_parser():
                         help="train_segnet.py --split_planes for the training rounds (float32 only)")
     parser.add_argument('--label_split_planes', action='store_true', default=False,
                         help="labels_from_segnet.py --split_planes for the labelling passes (--label_dtype fp32 only)")
+    parser.add_argument('--loader_procs', type=int, default=0,
+                        help="train_segnet.py --loader_procs for the training rounds: decode workers PER RANK "
+                             "(keep n_gpus x loader_procs within the CPUs the job has); 0: none")
     parser.add_argument('--n_labels', type=int, default=None, help='images to relabel (default: the split size)')
     parser.add_argument('--no_figure', action='store_true', default=False)
     parser.add_argument('--child_timeout', type=float, default=0,
@@ -212,6 +217,8 @@ def train_argv(args, step, result_dir, dirs):
         a.append('--random')
     if args.split_planes:
         a.append('--split_planes')
+    if args.loader_procs:
+        a += ['--loader_procs', str(args.loader_procs)]
     return a
 
 
