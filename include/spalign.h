@@ -554,6 +554,15 @@ int spa_segnet_decode_f16x3(spa_ctx *ctx, const float *x, const uint8_t *idx, in
  * (B,2,H,W) float32 the resized probabilities or NULL.  Upscales only (H >= h, W >= w): SPA_ERR_ARG otherwise. */
 int spa_segnet_score(spa_ctx *ctx, const float *prob, int32_t B, int32_t h, int32_t w, int32_t H, int32_t W,
                      uint8_t *mask, float *scores, void *stream);
+/* spa_segnet_score, the class map of the raw labelIds and spa_confusion in one launch (labels_from_segnet.py
+ * --loader_procs, train_segnet.py's validation).  mask and scores (NULL: not written) have spa_segnet_score's bits.
+ * label_ids (B,H,W) uint8, the bytes of the labelIds image: ids 0..6 are ignored, 7 is road, every other value (255
+ * included) non-road (segnet.label_mask); counts (B,4) int64 = {TN, FP, FN, TP} of mask against that map, what
+ * spa_confusion gives for it (zeroed on the stream first; integer atomics, so the sums do not depend on the order).
+ * label_ids and counts are NULL together (then only mask and scores are written).  The same limits and the same
+ * refusal of a downscale as spa_segnet_score: SPA_ERR_ARG, nothing launched.  No host synchronisation. */
+int spa_segnet_label_eval(spa_ctx *ctx, const float *prob, int32_t B, int32_t h, int32_t w, int32_t H, int32_t W,
+                          const uint8_t *label_ids, uint8_t *mask, float *scores, int64_t *counts, void *stream);
 
 /* ---- SegNet-Basic training input stage (train_segnet.py --loader_procs; csrc/spa_segnet_input.hip) --------------
  * What segnet_train.ZippedEstimatedCityscapesDataset.get_example computes on the host from a decoded frame, with

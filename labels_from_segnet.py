@@ -12,7 +12,11 @@ Outputs per image, in --out_dir:
   result.json             one JSON line per image, the reference's keys in its order (with --dtype bf16 one more key
                           after them, "dtype": "bf16"; with --split_planes one more, "split_planes": true; plain float32
                           lines are the reference's keys only)
-Additions: --no_figure, --batchsize (images per launch chain), --dtype {fp32,bf16} (the precision of the convolutions'
+Additions: --loader_procs N (default 0: the loop decodes every PNG itself and scores every image with a launch and a
+synchronisation of its own; N > 0: N worker processes decode the frames and the labelIds images a few batches ahead into
+pinned shared-memory slabs, superpixel-align_amd/segnet_loader.py LabelLoader, the mask, the scores and the confusion
+counts of a batch come from one launch, spa_segnet_label_eval, and the files of a batch are written while the next one
+is on the device; the outputs are the same, byte for byte), --no_figure, --batchsize (images per launch chain), --dtype {fp32,bf16} (the precision of the convolutions'
 operands: fp32, the default, the float32 matrix cores; bf16 every product operand rounded to bf16 with float32
 accumulation, see include/spalign.h spa_segnet_encode_bf16), --split_planes (float32 accuracy on the f16 matrix cores:
 every operand as two scaled half-precision planes, three products per float32 product, spa_segnet_encode_f16x3; the
@@ -24,6 +28,7 @@ import importlib
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -56,10 +61,78 @@ def _save_figure(d, i, pred, label, out_dir):
     plt.close()
 
 
+def _loader_run(torch, segnet, eng, model, loader, in_shape, eval_shape_t, save_each, emit, host_batch, result_path,
+                times):
+    """save_labels with --loader_procs: batch k goes slab -> resize -> network -> segnet_label_eval -> non-blocking
+    copies into one of two pinned host buffer sets, and while it is on the device the host writes batch k-1's outputs
+    (one event wait and one open of the result file per batch).  A batch the loader marks for the host path, or whose
+    labels are not of eval_shape (the plain loop's ValueError), goes through host_batch after the batch before it has
+    been written, so files, on_labels calls and JSON lines keep the index order.  -> the number of such batches.
+    times: seconds spent waiting for the loader, waiting for the device and writing the outputs are added to its
+    'loader_wait_s', 'device_wait_s' and 'output_s'."""
+    clock = time.perf_counter
+    B = loader.B
+    ring = []
+    for _ in range(2):
+        ring.append({'mask': torch.empty((B,) + eval_shape_t, dtype=torch.uint8).pin_memory(),
+                     'scores': None if save_each else torch.empty((B, 2) + eval_shape_t,
+                                                                  dtype=torch.float32).pin_memory(),
+                     'counts': torch.empty((B, 4), dtype=torch.int64).pin_memory()})
+    pending = [None]
+
+    def flush():
+        rec, pending[0] = pending[0], None
+        if rec is None:
+            return
+        t0 = clock()
+        rec['event'].synchronize()
+        t1 = clock()
+        buf = rec['buf']
+        mask_h, counts_h = buf['mask'].numpy(), buf['counts'].numpy()
+        sc_h = buf['scores'].numpy() if buf['scores'] is not None else None
+        with open(result_path, 'a') as fp:
+            for j, i in enumerate(rec['indices']):
+                label = segnet.label_mask(rec['ids_host'][j]) if rec['ids_host'] is not None else None
+                emit(i, mask_h[j], sc_h[j] if sc_h is not None else None, label, counts_h[j], fp)
+        times['device_wait_s'] += t1 - t0
+        times['output_s'] += clock() - t1
+
+    n_host = k = 0
+    batches = loader.batches()
+    while True:
+        t0 = clock()
+        batch = next(batches, None)
+        times['loader_wait_s'] += clock() - t0
+        if batch is None:
+            break
+        if batch.host or tuple(batch.label_ids.shape[1:]) != eval_shape_t:
+            flush()
+            n_host += 1
+            host_batch(batch.indices)
+            continue
+        n = len(batch.indices)
+        x = eng.resize_cvcubic_u8(batch.frames, in_shape)
+        prob = model.forward(x)
+        mask, sc, counts = eng.segnet_label_eval(prob, eval_shape_t, batch.label_ids, want_scores=not save_each)
+        buf = ring[k % 2]
+        k += 1
+        buf['mask'][:n].copy_(mask, non_blocking=True)
+        buf['counts'][:n].copy_(counts, non_blocking=True)
+        if sc is not None:
+            buf['scores'][:n].copy_(sc, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        rec = {'indices': batch.indices, 'ids_host': batch.ids_host, 'buf': buf, 'event': event}
+        flush()                                          # batch k-1's files while batch k is on the device
+        pending[0] = rec
+    flush()
+    return n_host
+
+
 def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
                 start_index, end_index, soft_label, eval_shape,
                 save_each=False, figure=True, batchsize=4, result_fn=None, on_labels=None,
-                split_planes=False, dtype='fp32'):
+                loader_procs=0, loader_stats=None, split_planes=False, dtype='fp32'):
     """labels_from_segnet.py:24-153.  With save_each=False returns {<out_dir>/<basename>: bool mask,
     <out_dir>/<basename>_scores: float32 (2, H, W) probabilities at eval_shape}.  result_fn: the file the JSON lines
     are appended to (default <out_dir>/result.json; utils/run_train_rounds.py gives each labelling process its own).
@@ -67,7 +140,11 @@ def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
     order, instead of collecting them in the returned dict (which stays empty), so a long range needs the memory of
     one batch only.  dtype: 'fp32' (default) or 'bf16', the network's convolution precision (segnet.SegNetBasic);
     bf16 adds "dtype": "bf16" to every JSON line.  split_planes (dtype 'fp32' only): the float32-accurate
-    convolutions on the f16 matrix cores; adds "split_planes": true to every JSON line."""
+    convolutions on the f16 matrix cores; adds "split_planes": true to every JSON line.  loader_procs N > 0: N worker
+    processes decode the frames and labelIds images ahead of the network and everything after it is one launch per batch
+    (_loader_run); the outputs are the plain loop's.  loader_stats: a dict that receives loop_s (the wall time of the
+    batch loop) and, from a loader run, n_host_batches (batches that took the plain loop's path), pinned, worker_pids and
+    the loop's loader_wait_s, device_wait_s and output_s."""
     import torch
     segnet = importlib.import_module('superpixel-align_amd.segnet')
     cli = importlib.import_module('superpixel-align_amd.cli')
@@ -96,8 +173,59 @@ def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
 
     pred_and_scores = {} if not save_each else None
     batchsize = max(int(batchsize), 1)
-    for lo in range(start_index, end_index, batchsize):
-        ids = list(range(lo, min(lo + batchsize, end_index)))
+    result_path = result_fn or os.path.join(out_dir, 'result.json')
+
+    def emit(i, pred, score, label, conf, fp):
+        """one image's outputs: pred uint8 (H,W), score float32 (2,H,W) or None, label int32 (H,W) (the figure's),
+        conf (TN, FP, FN, TP); the JSON line goes to fp"""
+        sc = cli.score_from_counts(*[int(v) for v in conf])
+        pred = pred.astype(bool)
+        fn_base = os.path.splitext(os.path.basename(d.img_fns[i]))[0]
+        save_fn = os.path.join(out_dir, fn_base)
+        if save_each:
+            np.save(save_fn, pred)
+            np.save(save_fn + '_scores', pred)       # sic: the reference saves the mask under this name too
+        elif on_labels is not None:
+            on_labels(save_fn, pred)
+            on_labels(save_fn + '_scores', score.astype(np.float32))
+        else:
+            pred_and_scores[save_fn] = pred
+            pred_and_scores[save_fn + '_scores'] = score.astype(np.float32)
+        if figure:
+            _save_figure(d, i, pred, label, out_dir)
+        result_info = {
+            'img_fn': d.img_fns[i],
+            'label_fn': d.label_fns[i],
+            'road_iou': sc['road_iou'],
+            'non_road_iou': sc['non_road_iou'],
+            'precision': sc['precision'],
+            'recall': sc['recall'],
+            'TP': sc['TP'],
+            'FP': sc['FP'],
+            'FN': sc['FN'],
+        }
+        result_info.update({
+            'param_dir': param_dir,
+            'iteration': iteration,
+            'gpu': gpu,
+            'img_zip_fn': img_zip_fn,
+            'label_zip_fn': label_zip_fn,
+            'out_dir': out_dir,
+            'start_index': start_index,
+            'end_index': end_index,
+            'soft_label': soft_label,
+            'eval_shape': eval_shape,
+            'save_each': save_each,
+        })
+        result_info.update({'train_args': train_args})
+        if dtype != 'fp32':
+            result_info['dtype'] = dtype
+        if split_planes:
+            result_info['split_planes'] = True
+        print(json.dumps(result_info), file=fp)
+
+    def host_batch(ids):
+        """the plain loop's batch: decoded here, one confusion launch and one synchronisation per image"""
         raws = [d.get_raw(i) for i in ids]
         # images of one size go through one launch chain (Cityscapes: all of them)
         groups = {}
@@ -122,55 +250,45 @@ def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
                                  % (d.label_fns[i], label.shape, pred.shape))
             conf = eng.confusion(torch.from_numpy(pred[None]).to(eng.device),
                                  torch.from_numpy(np.ascontiguousarray(label[None])).to(eng.device)).cpu().numpy()[0]
-            sc = cli.score_from_counts(*[int(v) for v in conf])
-            pred = pred.astype(bool)
-            fn_base = os.path.splitext(os.path.basename(d.img_fns[i]))[0]
-            save_fn = os.path.join(out_dir, fn_base)
-            if save_each:
-                np.save(save_fn, pred)
-                np.save(save_fn + '_scores', pred)       # sic: the reference saves the mask under this name too
-            elif on_labels is not None:
-                on_labels(save_fn, pred)
-                on_labels(save_fn + '_scores', scores[j].astype(np.float32))
-            else:
-                pred_and_scores[save_fn] = pred
-                pred_and_scores[save_fn + '_scores'] = scores[j].astype(np.float32)
-            if figure:
-                _save_figure(d, i, pred, label, out_dir)
-            with open(result_fn or os.path.join(out_dir, 'result.json'), 'a') as fp:
-                result_info = {
-                    'img_fn': d.img_fns[i],
-                    'label_fn': d.label_fns[i],
-                    'road_iou': sc['road_iou'],
-                    'non_road_iou': sc['non_road_iou'],
-                    'precision': sc['precision'],
-                    'recall': sc['recall'],
-                    'TP': sc['TP'],
-                    'FP': sc['FP'],
-                    'FN': sc['FN'],
-                }
-                result_info.update({
-                    'param_dir': param_dir,
-                    'iteration': iteration,
-                    'gpu': gpu,
-                    'img_zip_fn': img_zip_fn,
-                    'label_zip_fn': label_zip_fn,
-                    'out_dir': out_dir,
-                    'start_index': start_index,
-                    'end_index': end_index,
-                    'soft_label': soft_label,
-                    'eval_shape': eval_shape,
-                    'save_each': save_each,
-                })
-                result_info.update({'train_args': train_args})
-                if dtype != 'fp32':
-                    result_info['dtype'] = dtype
-                if split_planes:
-                    result_info['split_planes'] = True
-                print(json.dumps(result_info), file=fp)
+            with open(result_path, 'a') as fp:
+                emit(i, pred, scores[j], label, conf, fp)
+
+    loader = None
+    if int(loader_procs) > 0 and end_index > start_index:
+        sl = importlib.import_module('superpixel-align_amd.segnet_loader')
+        try:
+            loader = sl.LabelLoader(d, range(start_index, end_index), batchsize, int(loader_procs),
+                                    sl.DeviceLabelStage(eng), keep_ids=figure)
+        except cli.ShmTooSmall as e:
+            print('--loader_procs: %s; the images are decoded on the host' % e, flush=True)
+    times = {'loader_wait_s': 0.0, 'device_wait_s': 0.0, 'output_s': 0.0}
+    t_loop = time.perf_counter()
+    if loader is None:
+        for lo in range(start_index, end_index, batchsize):
+            host_batch(list(range(lo, min(lo + batchsize, end_index))))
+    else:
+        try:
+            n_host = _loader_run(torch, segnet, eng, model, loader, in_shape, eval_shape_t, save_each, emit, host_batch,
+                                 result_path, times)
+        finally:
+            if loader_stats is not None:
+                loader_stats.update(pinned=loader.pinned, worker_pids=list(loader.worker_pids))
+            loader.close()
+        if loader_stats is not None:
+            loader_stats['n_host_batches'] = n_host
+            loader_stats.update(times)
+    if loader_stats is not None:
+        loader_stats['loop_s'] = time.perf_counter() - t_loop       # the batches only: no model load, no worker start
     del model
     if not save_each:
         return pred_and_scores
+
+
+def _non_negative(v):
+    n = int(v)
+    if n < 0:
+        raise argparse.ArgumentTypeError('must be >= 0, got %d' % n)
+    return n
 
 
 def get_parser():
@@ -189,6 +307,8 @@ def get_parser():
     parser.add_argument('--batchsize', type=int, default=4)
     parser.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
     parser.add_argument('--split_planes', action='store_true', default=False)
+    parser.add_argument('--loader_procs', type=_non_negative, default=0,
+                        help='decode worker processes that feed the network; 0: the loop decodes every image itself')
     return parser
 
 
@@ -201,4 +321,4 @@ if __name__ == '__main__':
         args.param_dir, args.iteration, args.gpu, args.img_zip_fn,
         args.label_zip_fn, args.out_dir, args.start_index, args.end_index,
         args.soft_label, args.eval_shape, True, figure=not args.no_figure, batchsize=args.batchsize,
-        split_planes=args.split_planes, dtype=args.dtype)
+        split_planes=args.split_planes, dtype=args.dtype, loader_procs=args.loader_procs)

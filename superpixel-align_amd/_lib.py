@@ -139,6 +139,7 @@ PROTOTYPES = {
                                                c_p]),
     'spa_segnet_decode_f16x3': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
     'spa_segnet_score': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
+    'spa_segnet_label_eval': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p]),
     'spa_segnet_train_input': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p,
                                               c_p, c_i32, c_p, c_p, c_p, c_p, c_p]),
     'spa_segnet_train_label': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p,

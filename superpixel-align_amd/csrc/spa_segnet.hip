@@ -102,6 +102,137 @@ __global__ __launch_bounds__(256) void k_segnet_score(const float *__restrict__ 
     }
 }
 
+// k_segnet_score, the class map of segnet.label_mask on the raw labelIds bytes and k_confusion in one pass.  A block
+// is 64 x 4 threads over a tile of 256 columns x SG_LE_ROWS rows: a thread owns four adjacent columns, keeps their
+// horizontal coefficients and walks rows ty, ty + 4, ...  Every sample is formed by k_segnet_score's operations in its
+// order, so mask and scores have its bits.  VEC (W a multiple of 4, bases aligned): one 4-byte label load, one 4-byte
+// mask store and two 16-byte score stores per thread and row; otherwise bytes and dwords.  The counts are integers:
+// registers, wave shuffles, LDS across the four waves, one 64-bit atomicAdd per block and class.
+#define SG_LE_ROWS 16
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_segnet_label_eval(const float *__restrict__ P, int h, int w, int H, int W,
+                                                           const uint8_t *__restrict__ ids, uint8_t *__restrict__ mask,
+                                                           float *__restrict__ S, unsigned long long *__restrict__ counts)
+{
+    __shared__ unsigned sc[4][4];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, b = blockIdx.z;
+    const int xb = (blockIdx.x * 64 + tx) * 4;
+    const int yb = blockIdx.y * SG_LE_ROWS;
+    double kx[4][3];
+    int x0[4], nx[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int x = xb + p < W ? xb + p : W - 1;     // columns past the edge: a valid column, never stored
+        const int bx = sg_pil_coeffs(x, w, (double)w / (double)W, kx[p]);
+        x0[p] = bx & 0xffffff;
+        nx[p] = bx >> 24;
+    }
+    unsigned c[4] = {0, 0, 0, 0};
+    const long long plane = (long long)H * W;
+    if (xb < W) {
+        for (int r = ty; r < SG_LE_ROWS; r += 4) {
+            const int y = yb + r;
+            if (y >= H) break;
+            double ky[3];
+            const int by = sg_pil_coeffs(y, h, (double)h / (double)H, ky);
+            const int y0 = by & 0xffffff, ny = by >> 24;
+            float out[2][4];
+#pragma unroll
+            for (int ch = 0; ch < 2; ++ch) {
+                const float *pc = P + ((long long)b * 2 + ch) * h * w;
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    double sv = 0.0;
+                    for (int j = 0; j < ny; ++j) {
+                        const float *row = pc + (long long)(y0 + j) * w + x0[p];
+                        double sh = 0.0;
+                        for (int i = 0; i < nx[p]; ++i) sh += (double)row[i] * kx[p][i];
+                        sv += (double)(float)sh * ky[j];
+                    }
+                    out[ch][p] = (float)sv;
+                }
+            }
+            const long long o = ((long long)b * H + y) * W + xb;
+            uint8_t m[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) m[p] = out[1][p] > out[0][p] ? 1 : 0;      // argmax, ties to class 0
+            uint8_t g[4] = {0, 0, 0, 0};
+            if (VEC) {
+                *(uint32_t *)(mask + o) = (uint32_t)m[0] | ((uint32_t)m[1] << 8) | ((uint32_t)m[2] << 16) |
+                                          ((uint32_t)m[3] << 24);
+                if (S) {
+                    float *s0 = S + (long long)b * 2 * plane + (long long)y * W + xb;
+                    *(float4 *)s0 = make_float4(out[0][0], out[0][1], out[0][2], out[0][3]);
+                    *(float4 *)(s0 + plane) = make_float4(out[1][0], out[1][1], out[1][2], out[1][3]);
+                }
+                if (ids) {
+                    const uint32_t v = *(const uint32_t *)(ids + o);
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) g[p] = (uint8_t)(v >> (8 * p));
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    if (xb + p >= W) break;
+                    mask[o + p] = m[p];
+                    if (S) {
+                        float *s0 = S + (long long)b * 2 * plane + (long long)y * W + xb + p;
+                        s0[0] = out[0][p];
+                        s0[plane] = out[1][p];
+                    }
+                    if (ids) g[p] = ids[o + p];
+                }
+            }
+            if (ids) {
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+                    if (xb + p < W && g[p] > 6) c[(g[p] == 7 ? 2 : 0) + m[p]] += 1;   // ids 0..6 are ignored
+            }
+        }
+    }
+    if (!counts) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        for (int o = 32; o > 0; o >>= 1) c[j] += __shfl_down(c[j], o);
+    if (tx == 0)
+        for (int j = 0; j < 4; ++j) sc[ty][j] = c[j];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const unsigned t = sc[0][threadIdx.x] + sc[1][threadIdx.x] + sc[2][threadIdx.x] + sc[3][threadIdx.x];
+        if (t) atomicAdd(counts + (long long)b * 4 + threadIdx.x, (unsigned long long)t);
+    }
+}
+
+extern "C" int spa_segnet_label_eval(spa_ctx *ctx, const float *prob, int32_t B, int32_t h, int32_t w, int32_t H,
+                                     int32_t W, const uint8_t *label_ids, uint8_t *mask, float *scores, int64_t *counts,
+                                     void *stream)
+{
+    SPA_ARG(ctx && prob && mask && B > 0 && B < 65536 && h > 0 && w > 0 && H > 0 && W > 0);
+    SPA_ARG(H < 65536 && W < (1 << 24) && h < (1 << 24) && w < (1 << 24));
+    if ((label_ids == nullptr) != (counts == nullptr)) {
+        spa_set_error("spa_segnet_label_eval: label_ids and counts must be given together or both be NULL");
+        return SPA_ERR_ARG;
+    }
+    if (H < h || W < w) {
+        spa_set_error("spa_segnet_label_eval: (%d, %d) -> (%d, %d) is a downscale; only upscales are supported", h, w, H,
+                      W);
+        return SPA_ERR_ARG;
+    }
+    hipStream_t s = spa_stream(stream);
+    if (counts) SPA_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(int64_t), s));
+    const bool vec = W % 4 == 0 && (((uintptr_t)mask | (uintptr_t)label_ids) & 3) == 0 && ((uintptr_t)scores & 15) == 0;
+    const dim3 grid((W + 255) / 256, (H + SG_LE_ROWS - 1) / SG_LE_ROWS, B);
+    if (vec)
+        hipLaunchKernelGGL(k_segnet_label_eval<true>, grid, dim3(256), 0, s, prob, h, w, H, W, label_ids, mask, scores,
+                           (unsigned long long *)counts);
+    else
+        hipLaunchKernelGGL(k_segnet_label_eval<false>, grid, dim3(256), 0, s, prob, h, w, H, W, label_ids, mask, scores,
+                           (unsigned long long *)counts);
+    SPA_LAUNCH_CHECK();
+    return SPA_OK;
+}
+
 extern "C" int spa_segnet_encode(spa_ctx *ctx, const float *x, int32_t x_layout, int32_t B, int32_t H, int32_t W,
                                  int32_t Cin, const float *wt, const float *bias, const float *mean_host,
                                  const float *std_host, float *pooled, uint8_t *idx, void *stream)

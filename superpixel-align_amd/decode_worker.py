@@ -57,6 +57,24 @@ def decode_into(task):
     return tuple(a.shape)
 
 
+def png_into(task):
+    """(shm name, byte offset, expected array shape, expected Pillow mode, source) -> (array shape, mode) of the image.
+    For a PNG whose mode matters (segnet_loader.LabelLoader): 'RGB' for a frame, (H, W, 3), 'L' for a labelIds image,
+    (H, W).  For these two modes np.asarray(f) is what convert('RGB') / convert('L') give, so the image is written at
+    the offset only when both its shape and its mode are the expected ones; the caller falls back otherwise."""
+    from PIL import Image
+    name, offset, shape, mode, src = task
+    with Image.open(_open(src)) as f:
+        got_mode = f.mode
+        got_shape = (f.size[1], f.size[0]) + ((len(f.getbands()),) if len(f.getbands()) > 1 else ())
+        if got_mode != mode or got_shape != tuple(shape):
+            return got_shape, got_mode
+        a = np.asarray(f, dtype=np.uint8)
+    dst = np.ndarray(shape, dtype=np.uint8, buffer=_attach(name).buf, offset=offset)
+    dst[...] = a
+    return tuple(a.shape), got_mode
+
+
 def label_into(task):
     """(shm name, byte offset, expected shape, (zip path, member name)) -> (shape, dtype string) of the .npy member
     of an npz-style label zip (cli.write_label_zip, run_train_rounds.py): a 2-D road mask of bool or uint8, or a

@@ -893,6 +893,28 @@ class Engine(object):
         check(self._lib.spa_segnet_score(self._ctx, _ptr(prob), B, h, w, H, W, _ptr(mask), _ptr(sc), self._s()))
         return mask, sc
 
+    def segnet_label_eval(self, prob, shape, label_ids=None, want_scores=False):
+        """segnet_score and, with label_ids (B,H,W) uint8 (the raw labelIds bytes), the confusion of the mask against
+        segnet.label_mask(label_ids), in one launch -> (mask (B,H,W) uint8, scores (B,2,H,W) float32 or None, counts
+        (B,4) int64 {TN, FP, FN, TP} or None).  mask and scores have segnet_score's bits, counts are
+        confusion(mask, label_mask(ids))."""
+        prob = _req(prob, torch.float32, 'prob')
+        B, C, h, w = prob.shape
+        assert C == 2
+        H, W = int(shape[0]), int(shape[1])
+        counts = None
+        if label_ids is not None:
+            label_ids = _req(label_ids, torch.uint8, 'label_ids')
+            if tuple(label_ids.shape) != (B, H, W):
+                raise SpalignError('segnet_label_eval: label_ids must be %s uint8, got %s'
+                                   % ((B, H, W), tuple(label_ids.shape)))
+            counts = torch.empty((B, 4), dtype=torch.int64, device=prob.device)
+        mask = torch.empty((B, H, W), dtype=torch.uint8, device=prob.device)
+        sc = torch.empty((B, 2, H, W), dtype=torch.float32, device=prob.device) if want_scores else None
+        check(self._lib.spa_segnet_label_eval(self._ctx, _ptr(prob), B, h, w, H, W, _ptr(label_ids), _ptr(mask),
+                                              _ptr(sc), _ptr(counts), self._s()))
+        return mask, sc, counts
+
     # ---- SegNet-Basic training input stage (segnet_loader.py): get_example's arithmetic on decoded batches
     def _input_tables(self, kind, n_in, n_out, backend):
         """Device tables of one axis, uploaded once per (kind, n_in, n_out, backend): 'cubic' -> (bounds, taps, ksize)

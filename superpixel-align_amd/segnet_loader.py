@@ -21,6 +21,10 @@ What keeps the bits:
     functions with the draws already made.
 HostStage runs the device stage's arithmetic with the dataset's numpy and Pillow functions (no GPU): the tests of
 the draw order use it, with real workers.
+
+LabelLoader feeds the two loops that read a ZippedCityscapesRoadDataset with get_raw (labels_from_segnet.save_labels
+and train_segnet.evaluate, --loader_procs) the same way: frames and raw labelIds bytes, in index order, nothing drawn.
+Both loaders keep their slabs and workers in one helper, Slabs, and may share one WorkerPool.
 """
 import collections
 import os
@@ -173,17 +177,105 @@ class DeviceStage(object):
         self.side.synchronize()
 
 
+class WorkerPool(object):
+    """The spawned decode workers of one process (decode_worker.py), shared by its loaders: every user acquire()s it
+    and release()s it in its close(); the last release shuts it down.  spawn, not fork: the process may have
+    initialised the GPU.  The workers end with the process that made them (die_with_parent)."""
+
+    def __init__(self, n_procs):
+        import multiprocessing as mp
+        from concurrent.futures import ProcessPoolExecutor
+        self.n_procs = int(n_procs)
+        self.executor = ProcessPoolExecutor(max_workers=self.n_procs, mp_context=mp.get_context('spawn'),
+                                            initializer=decode_worker.die_with_parent, initargs=(os.getpid(),))
+        self.users = 0
+        self.pids = None
+
+    def acquire(self):
+        self.users += 1
+        return self
+
+    def warm(self):
+        """-> the workers' pids; the first call starts every worker and imports Pillow's PNG plugin in it"""
+        if self.pids is None:
+            self.pids = sorted(set(self.executor.map(decode_worker.warm, range(4 * self.n_procs))))
+        return self.pids
+
+    def release(self):
+        self.users -= 1
+        if self.users <= 0 and self.executor is not None:
+            self.executor.shutdown(wait=True, cancel_futures=True)
+            self.executor = None
+
+
+class Slabs(object):
+    """What a loader holds besides its batches: n_slabs shared-memory slabs of slab_bytes each (the caller counts one
+    spare, so a batch is never decoded into the slab whose upload was just enqueued), each registered with the stage
+    (DeviceStage: as pinned host memory, with one notice when that fails), and the worker pool, its own or the one
+    given.  Raises cli.ShmTooSmall where /dev/shm cannot hold the slabs, before anything else happens.  A
+    constructor that fails has closed what it had opened.  close() may be called any number of times."""
+
+    def __init__(self, what, slab_bytes, n_slabs, n_procs, stage, pool=None):
+        from multiprocessing import shared_memory
+        self.stage, self.slots, self.workers = stage, [], None
+        free = _shm_free()
+        if free is not None and free < n_slabs * slab_bytes + (16 << 20):
+            from .cli import ShmTooSmall
+            raise ShmTooSmall('/dev/shm has %d MB free, %s slabs need %d MB'
+                              % (free >> 20, what, (n_slabs * slab_bytes) >> 20))
+        try:
+            for _ in range(n_slabs):
+                shm = shared_memory.SharedMemory(create=True, size=slab_bytes)
+                slot = {'shm': shm, 'handle': None}
+                self.slots.append(slot)
+                slot['handle'] = stage.register(shm)
+            self.workers = (pool if pool is not None else WorkerPool(n_procs)).acquire()
+            self.pinned = all(s['handle']['pinned'] for s in self.slots)    # every slab is pinned host memory
+            self.worker_pids = self.workers.warm()
+        except BaseException:
+            self.close()
+            raise
+
+    def submit(self, fn, task):
+        return self.workers.executor.submit(fn, task)
+
+    def close(self, futures=()):
+        """futures: the owner's tasks still in flight; none of them writes into a slab after this returns"""
+        for f in futures:
+            f.cancel()
+        for f in futures:
+            if not f.cancelled():
+                try:
+                    f.exception()
+                except BaseException:
+                    pass
+        workers, self.workers = self.workers, None
+        if workers is not None:
+            workers.release()
+        slots, self.slots = self.slots, []
+        try:
+            self.stage.close()
+        finally:                                            # the slabs go whatever state the device is in
+            for s in slots:
+                if s['handle'] is not None:
+                    self.stage.unregister(s['handle'])
+                    s['handle'] = None
+                for release in (s['shm'].close, s['shm'].unlink):
+                    try:
+                        release()
+                    except Exception:
+                        pass
+
+
 class TrainLoader(object):
     """next() -> (images (B,3,h,w) float32, labels, (iterator state, numpy state) after that batch's draws): the plain
     loop's batches in its order.  dataset: a ZippedEstimatedCityscapesDataset; ids: the rank's example indices
     (train_ids); iterator: the ShuffledIterator the plain loop would call.  stage: a DeviceStage or a HostStage.
+    pool: a WorkerPool to share (another loader's .workers); None: n_procs workers of its own.
     Raises cli.ShmTooSmall where /dev/shm cannot hold the slabs, before anything is drawn.  close() stops the workers
     and unregisters and unlinks the slabs; call it in a finally."""
 
-    def __init__(self, dataset, ids, iterator, n_procs, stage, depth=None):
-        import multiprocessing as mp
-        from concurrent.futures import ProcessPoolExecutor
-        from multiprocessing import shared_memory
+    def __init__(self, dataset, ids, iterator, n_procs, stage, depth=None, pool=None):
         self.ds, self.ids, self.it, self.stage = dataset, np.asarray(ids), iterator, stage
         self.B = int(iterator.batchsize)
         self.depth = depth = int(depth or default_depth(n_procs, self.B))
@@ -196,30 +288,13 @@ class TrainLoader(object):
         self.shift_off = align(self.lab_off + self.B * self.lbytes)
         self.flip_off = self.shift_off + self.B * 24
         slab = align(self.flip_off + self.B)
-        free = _shm_free()
-        n_slabs = depth + 1                # one spare: a batch is never decoded into the slab whose upload was just enqueued
-        if free is not None and free < n_slabs * slab + (16 << 20):
-            from .cli import ShmTooSmall
-            raise ShmTooSmall('/dev/shm has %d MB free, the training loader\'s slabs need %d MB'
-                              % (free >> 20, (n_slabs * slab) >> 20))
         self.slots, self.free, self.pending = [], [], collections.deque()
-        self.pool = None
+        self.pool = self.slabs = None
         self.n_host_batches = 0            # batches that took the host path (another shape than the first example's)
-        try:
-            for _ in range(n_slabs):
-                shm = shared_memory.SharedMemory(create=True, size=slab)
-                slot = {'shm': shm, 'handle': None}
-                self.slots.append(slot)
-                slot['handle'] = stage.register(shm)
-                self.free.append(slot)
-            # spawn, not fork: this process may have initialised the GPU
-            self.pool = ProcessPoolExecutor(max_workers=int(n_procs), mp_context=mp.get_context('spawn'),
-                                            initializer=decode_worker.die_with_parent, initargs=(os.getpid(),))
-            self.pinned = all(s['handle']['pinned'] for s in self.slots)    # every slab is pinned host memory
-            self.worker_pids = sorted(set(self.pool.map(decode_worker.warm, range(4 * int(n_procs)))))
-        except BaseException:
-            self.close()
-            raise
+        self.slabs = Slabs('the training loader\'s', slab, depth + 1, n_procs, stage, pool)
+        self.slots, self.free = self.slabs.slots, list(self.slabs.slots)
+        self.workers, self.pool = self.slabs.workers, self.slabs.workers.executor
+        self.pinned, self.worker_pids = self.slabs.pinned, self.slabs.worker_pids
 
     def _views(self, slot):
         buf = np.frombuffer(slot['shm'].buf, dtype=np.uint8)
@@ -247,7 +322,7 @@ class TrainLoader(object):
         tasks += [(decode_worker.label_into, (name, self.lab_off + j * self.lbytes, self.lshape,
                                               (self.ds.label_zip_fn, self.ds.label_fns[i]))) for j, i in enumerate(ids)]
         self.pending.append({'ids': ids, 'shifts': shifts, 'flips': flips, 'state': state, 'slot': slot, 'out': None,
-                             'futures': [self.pool.submit(fn, t) for fn, t in tasks]})
+                             'futures': [self.slabs.submit(fn, t) for fn, t in tasks]})
 
     def _fill(self):
         while self.free and len(self.pending) < self.depth:
@@ -295,21 +370,183 @@ class TrainLoader(object):
         return img, lab, rec['state']
 
     def close(self):
-        if self.pool is not None:
-            self.pool.shutdown(wait=True, cancel_futures=True)
-            self.pool = None
+        futures = [f for rec in self.pending for f in (rec['futures'] or ())]
+        self.pending.clear()
+        self.free, self.slots, self.pool = [], [], None
+        slabs, self.slabs = self.slabs, None
+        if slabs is not None:
+            slabs.close(futures)
+
+
+# ------------------------------------------------------------------------------- labelling and validation
+def _first_png_shapes(ds):
+    """((H, W, 3), (Hl, Wl)) of a ZippedCityscapesRoadDataset's first frame and labelIds image, from the headers"""
+    import zipfile
+    from PIL import Image
+    with zipfile.ZipFile(ds.img_zip_fn) as zf, Image.open(zf.open(ds.img_fns[0])) as f:
+        W, H = f.size
+    with zipfile.ZipFile(ds.label_zip_fn) as zf, Image.open(zf.open(ds.label_fns[0])) as f:
+        Wl, Hl = f.size
+    return (H, W, 3), (Hl, Wl)
+
+
+class LabelBatch(object):
+    """One batch of a LabelLoader.  indices: the dataset indices, in order.  host False: frames (n,H,W,3) uint8 and
+    label_ids (n,Hl,Wl) uint8, the stage's arrays (device tensors the current stream may use, or numpy copies), and
+    ids_host, a numpy copy of the label ids where the loader keeps one (else None).  host True: the batch holds a
+    member of another shape or mode and must go through the dataset's get_raw; the arrays are None."""
+
+    def __init__(self, indices):
+        self.indices, self.host = indices, False
+        self.frames = self.label_ids = self.ids_host = None
+
+
+class HostLabelStage(HostStage):
+    """numpy in, numpy out, no GPU: copies of the slab's frames and label ids."""
+
+    def __init__(self, dataset=None):
+        HostStage.__init__(self, dataset)
+
+    def run(self, handle, views, n):
+        return views[0][:n].copy(), views[1][:n].copy()
+
+
+class DeviceLabelStage(DeviceStage):
+    """One upload of the slab's frames and label ids on a side stream; finish() makes the current stream wait for it."""
+
+    def __init__(self, engine):
+        DeviceStage.__init__(self, None, engine)
+
+    def run(self, handle, views, n):
+        torch = self.torch
+        imgs, ids = views[0][:n], views[1][:n]
+        base = views[0].__array_interface__['data'][0]
+        off = ids.__array_interface__['data'][0] - base
+        with torch.cuda.stream(self.side):
+            d = handle['t'][:off + ids.nbytes].to(self.eng.device, non_blocking=True)
+            handle['ev'] = torch.cuda.Event()
+            handle['ev'].record(self.side)
+        return (d[:imgs.nbytes].view(tuple(imgs.shape)), d[off:off + ids.nbytes].view(tuple(ids.shape)), handle['ev'])
+
+    def finish(self, out):
+        frames, ids, ready = out
+        cur = self.torch.cuda.current_stream(self.eng.device)
+        cur.wait_event(ready)
+        frames.record_stream(cur)
+        return frames, ids
+
+
+class LabelLoader(object):
+    """The frames and labelIds images of a ZippedCityscapesRoadDataset's examples `indices`, in order, in batches of
+    `batchsize` (the last may be short), decoded by workers a few batches ahead (default_depth) into slabs: what
+    labels_from_segnet.save_labels and train_segnet.evaluate read with get_raw, one image after the other.
+    batches() yields LabelBatch objects; it may be called again for another pass over the same indices.  A batch with
+    a frame or label of another shape than the first example's, or of another mode than RGB / L (for which np.asarray
+    of the decoded image is not what get_raw's convert() gives), is marked host.  stage: a DeviceLabelStage or a
+    HostLabelStage.  pool: a WorkerPool to share (a TrainLoader's .workers).  keep_ids: every batch also carries a
+    numpy copy of its label ids.  Raises cli.ShmTooSmall like TrainLoader; close() in a finally."""
+
+    def __init__(self, dataset, indices, batchsize, n_procs, stage, depth=None, pool=None, keep_ids=False):
+        self.ds, self.indices, self.stage = dataset, [int(i) for i in indices], stage
+        self.B = max(int(batchsize), 1)
+        self.depth = depth = int(depth or default_depth(n_procs, self.B))
+        self.keep_ids = bool(keep_ids)
+        self.free, self.pending, self.pos = [], collections.deque(), 0
+        self.slabs = None
+        self.n_host_batches = 0
+        self.ishape, self.lshape = _first_png_shapes(dataset) if self.indices else ((1, 1, 3), (1, 1))
+        align = lambda n: (n + 63) // 64 * 64
+        self.ibytes, self.lbytes = int(np.prod(self.ishape)), int(np.prod(self.lshape))
+        self.lab_off = align(self.B * self.ibytes)
+        slab = align(self.lab_off + self.B * self.lbytes)
+        self.slabs = Slabs('the label loader\'s', slab, depth + 1, n_procs, stage, pool)
+        self.free = list(self.slabs.slots)
+        self.workers = self.slabs.workers
+        self.pinned, self.worker_pids = self.slabs.pinned, self.slabs.worker_pids
+
+    def _views(self, slot):
+        buf = np.frombuffer(slot['shm'].buf, dtype=np.uint8)
+        B = self.B
+        return (buf[:B * self.ibytes].reshape((B,) + self.ishape),
+                buf[self.lab_off:self.lab_off + B * self.lbytes].reshape((B,) + self.lshape))
+
+    def _submit(self):
+        ids = self.indices[self.pos:self.pos + self.B]
+        self.pos += len(ids)
+        slot = self.free.pop(0)
+        self.stage.wait(slot['handle'])
+        name = slot['shm'].name
+        tasks = [(name, j * self.ibytes, self.ishape, 'RGB', (self.ds.img_zip_fn, self.ds.img_fns[i]))
+                 for j, i in enumerate(ids)]
+        tasks += [(name, self.lab_off + j * self.lbytes, self.lshape, 'L', (self.ds.label_zip_fn, self.ds.label_fns[i]))
+                  for j, i in enumerate(ids)]
+        self.pending.append({'batch': LabelBatch(ids), 'slot': slot, 'out': None,
+                             'futures': [self.slabs.submit(decode_worker.png_into, t) for t in tasks]})
+
+    def _fill(self):
+        while self.free and len(self.pending) < self.depth and self.pos < len(self.indices):
+            self._submit()
+
+    def _stage(self, rec):
+        batch = rec['batch']
+        n = len(batch.indices)
+        got = [f.result() for f in rec['futures']]
+        rec['futures'] = None
+        slot, rec['slot'] = rec['slot'], None
+        want = [(self.ishape, 'RGB')] * n + [(self.lshape, 'L')] * n
+        if all((tuple(g[0]), g[1]) == w for g, w in zip(got, want)):
+            views = self._views(slot)
+            if self.keep_ids:
+                batch.ids_host = views[1][:n].copy()
+            rec['out'] = self.stage.run(slot['handle'], views, n)
+            del views
+        else:
+            batch.host = True
+            rec['out'] = ()
+            self.n_host_batches += 1
+        self.free.append(slot)
+
+    def _drain(self):
+        """an abandoned pass: its tasks end before their slabs are used again"""
+        for rec in self.pending:
+            for f in rec['futures'] or ():
+                f.cancel()
+            for f in rec['futures'] or ():
+                if not f.cancelled():
+                    try:
+                        f.exception()
+                    except BaseException:
+                        pass
+            if rec['slot'] is not None:
+                self.free.append(rec['slot'])
+        self.pending.clear()
+
+    def batches(self):
+        self._drain()
+        self.pos = 0
+        while True:
+            self._fill()
+            if not self.pending:
+                return
+            rec = self.pending.popleft()
+            if rec['out'] is None:
+                self._stage(rec)
+            self._fill()
+            # the batch after this one, when its decodes are done already: its upload overlaps this batch's work
+            if self.pending and self.pending[0]['out'] is None and all(f.done() for f in self.pending[0]['futures']):
+                self._stage(self.pending[0])
+                self._fill()
+            batch = rec['batch']
+            if not batch.host:
+                batch.frames, batch.label_ids = self.stage.finish(rec['out'])
+            yield batch
+
+    __iter__ = batches
+
+    def close(self):
+        futures = [f for rec in self.pending for f in (rec['futures'] or ())]
         self.pending.clear()
         self.free = []
-        slots, self.slots = self.slots, []
-        try:
-            self.stage.close()
-        finally:                                            # the slabs go whatever state the device is in
-            for s in slots:
-                if s['handle'] is not None:
-                    self.stage.unregister(s['handle'])
-                    s['handle'] = None
-                for release in (s['shm'].close, s['shm'].unlink):
-                    try:
-                        release()
-                    except Exception:
-                        pass
+        slabs, self.slabs = self.slabs, None
+        if slabs is not None:
+            slabs.close(futures)

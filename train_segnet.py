@@ -44,7 +44,9 @@ snapshots (they store the iterator and numpy state that belong to their iteratio
 --resume continues bit for bit from either kind of run with or without the flag.  args.txt records loader_procs only
 when it is given.  Under --data_parallel every rank has its own N workers: keep ranks x N within the CPUs the job has.
 A batch whose frames are not of the first frame's size takes the host path, and so does the whole run (it says so
-once) where /dev/shm cannot hold the slabs.
+once) where /dev/shm cannot hold the slabs.  The same workers feed the validation passes (segnet_loader.LabelLoader): the
+validation images go through the predictor in batches of --batchsize, the confusion counts come from
+spa_segnet_label_eval and are summed on the device, and every report entry is the default run's.
 """
 import argparse
 import importlib
@@ -200,25 +202,46 @@ def _iterations(interval, n_data, batchsize):
     raise ValueError('unknown interval unit %r' % unit)
 
 
-def evaluate(trainer, valid, eval_shape, batchsize, indices=None, split_planes=False):
+def evaluate(trainer, valid, eval_shape, batchsize, indices=None, split_planes=False, loader=None):
     """SemanticSegmentationEvaluator + PrecisionRecallEvaluator over the validation set (or its examples `indices`)
     with the inference network (BN folded from the running statistics), predicting as labels_from_segnet.py does ->
     the report entries.  split_planes: the predictor's float32-accurate convolutions on the f16 matrix cores
-    (--val_split_planes) instead of the float32 ones."""
+    (--val_split_planes) instead of the float32 ones.  loader: a segnet_loader.LabelLoader over the same indices
+    (--loader_procs): its batches of `batchsize` images go through the predictor together, segnet_label_eval's counts
+    are summed on the device and downloaded once; an image has the same bits in any batch and the counts are
+    integers, so the entries are the same.  Batches the loader marks for the host path take the per-image body."""
     import torch
     model = trainer.predictor(eval_shape, split_planes=True) if split_planes else trainer.predictor(eval_shape)
     eng = trainer.eng
     in_shape = tuple(int(v) for v in valid.resize_shape)
     indices = list(range(len(valid))) if indices is None else [int(i) for i in indices]
     conf = np.zeros(4, np.int64)                                    # TN, FP, FN, TP
-    for lo in range(0, len(indices), batchsize):
-        raws = [valid.get_raw(i) for i in indices[lo:lo + batchsize]]
+
+    def host_images(ids):
+        raws = [valid.get_raw(i) for i in ids]
         for img, label in raws:
             u8 = torch.from_numpy(np.ascontiguousarray(img.transpose(1, 2, 0))[None]).to(eng.device)
             x = eng.resize_cvcubic_u8(u8.contiguous(), in_shape)
             mask, _ = eng.segnet_score(model.forward(x), tuple(eval_shape))
             gt = torch.from_numpy(np.ascontiguousarray(label[None])).to(eng.device)
-            conf += eng.confusion(mask, gt).cpu().numpy()[0]
+            conf[...] += eng.confusion(mask, gt).cpu().numpy()[0]
+
+    if loader is None:
+        for lo in range(0, len(indices), batchsize):
+            host_images(indices[lo:lo + batchsize])
+    else:
+        if list(loader.indices) != indices:
+            raise ValueError('evaluate: the loader was opened over other indices than the ones to evaluate')
+        shape = tuple(int(v) for v in eval_shape)
+        total = torch.zeros(4, dtype=torch.int64, device=eng.device)
+        for batch in loader.batches():
+            if batch.host or tuple(batch.label_ids.shape[1:]) != shape:
+                host_images(batch.indices)
+                continue
+            x = eng.resize_cvcubic_u8(batch.frames, in_shape)
+            _, _, counts = eng.segnet_label_eval(model.forward(x), shape, batch.label_ids)
+            total += counts.sum(0)
+        conf += total.cpu().numpy()                                 # the one download of a validation
     TN, FP, FN, TP = [int(v) for v in conf]
     with np.errstate(divide='ignore', invalid='ignore'):
         iou_road = TP / float(TP + FP + FN) if TP + FP + FN else float('nan')
@@ -249,6 +272,18 @@ def open_loader(n_procs, train, train_ids, it, stage):
         return sl.TrainLoader(train, train_ids, it, n_procs, stage)
     except cli.ShmTooSmall as e:
         print('--loader_procs: %s; the batches are prepared on the host' % e, flush=True)
+        return None
+
+
+def open_label_loader(n_procs, valid, valid_ids, batchsize, stage, pool=None):
+    """-> the run's segnet_loader.LabelLoader over the rank's validation indices (on the training loader's workers
+    where `pool` is given), or None where /dev/shm cannot hold its slabs: one line, and validation decodes on the host"""
+    sl = importlib.import_module('superpixel-align_amd.segnet_loader')
+    cli = importlib.import_module('superpixel-align_amd.cli')
+    try:
+        return sl.LabelLoader(valid, valid_ids, batchsize, n_procs, stage, pool=pool)
+    except cli.ShmTooSmall as e:
+        print('--loader_procs: %s; the validation images are decoded on the host' % e, flush=True)
         return None
 
 
@@ -344,13 +379,17 @@ def main(argv=None):
     val_every = _iterations(args.val_interval, len(train_ids), args.batchsize)
     decay = args.decay_iteration if args.optimizer == 'MomentumSGD' else 0
     dev = trainer.eng.device
-    loader = None
+    loader = val_loader = None
     if pre.loader_procs:                           # after --resume has set the iterator and numpy's state
         sl = importlib.import_module('superpixel-align_amd.segnet_loader')
         loader = open_loader(pre.loader_procs, train, train_ids, it, sl.DeviceStage(train, trainer.eng))
     # loader None: every batch is prepared here; else loader.next() hands out the same batches, each with the (iterator
     # state, numpy state) the plain loop has after it, which the log and the snapshots then use
     try:
+        if pre.loader_procs and len(valid_ids):    # validation reads from the same workers
+            val_loader = open_label_loader(pre.loader_procs, valid, valid_ids, args.batchsize,
+                                           sl.DeviceLabelStage(trainer.eng),
+                                           pool=loader.workers if loader is not None else None)
         losses = []
         t0 = time.time()
         while iteration < stop:
@@ -370,7 +409,7 @@ def main(argv=None):
             report = {}
             if iteration % val_every == 0:
                 report.update(evaluate(trainer, valid, args.eval_shape, args.batchsize, valid_ids,
-                                       split_planes=pre.val_split_planes))
+                                       split_planes=pre.val_split_planes, loader=val_loader))
                 if group is not None:
                     report = group.mean_over_ranks(report)               # create_multi_node_evaluator: mean over ranks
             if iteration % log_every == 0:
@@ -395,6 +434,8 @@ def main(argv=None):
                     st.save_snapshot(os.path.join(result_dir, 'snapshot_iter_{}'.format(iteration)), trainer, iteration,
                                      opt.lr, it_state, extra, np_state)
     finally:
+        if val_loader is not None:
+            val_loader.close()
         if loader is not None:
             loader.close()
     if group is not None:

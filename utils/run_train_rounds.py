@@ -34,7 +34,9 @@ convolution passes on split f16 planes; passed to the training children only whe
 labelling passes' labels_from_segnet.py --split_planes: float32-accurate inference on the f16 matrix cores;
 independent of --split_planes and --dtype, refused with --label_dtype bf16), --loader_procs (the training rounds'
 train_segnet.py --loader_procs: decode workers per rank and the input stage on the GPU, passed only when given; the
-job needs n_gpus x loader_procs CPUs for them), --n_labels (overrides the
+job needs n_gpus x loader_procs CPUs for them; they also feed those rounds' validation), --label_loader_procs (the
+labelling passes' labels_from_segnet.py --loader_procs: decode workers per labelling process, independent of
+--loader_procs; the job needs n_gpus x label_loader_procs CPUs for them), --n_labels (overrides the
 split's constant), --no_figure (the labellers' 3-panel figures), --child_timeout.
 plan() computes the rounds, their commands, resume paths, result-directory prefixes and zip names without launching
 anything.
@@ -100,6 +102,10 @@ def get_parser():
     parser.add_argument('--loader_procs', type=int, default=0,
                         help="train_segnet.py --loader_procs for the training rounds: decode workers PER RANK "
                              "(keep n_gpus x loader_procs within the CPUs the job has); 0: none")
+    parser.add_argument('--label_loader_procs', type=int, default=0,
+                        help="labels_from_segnet.py --loader_procs for the labelling passes: decode workers PER "
+                             "LABELLING PROCESS; the job needs n_gpus x label_loader_procs CPUs for the decode workers; "
+                             "0: none")
     parser.add_argument('--n_labels', type=int, default=None, help='images to relabel (default: the split size)')
     parser.add_argument('--no_figure', action='store_true', default=False)
     parser.add_argument('--child_timeout', type=float, default=0,
@@ -330,7 +336,8 @@ def label_worker(spec):
                     spec['out_dir'], spec['start'], spec['end'], spec['soft_label'], spec['eval_shape'],
                     spec['save_each'], figure=spec['figure'], result_fn=os.path.join(spool, 'result.json'),
                     on_labels=None if spec['save_each'] else spool_one,
-                    split_planes=spec.get('split_planes', False), dtype=spec['dtype'])
+                    split_planes=spec.get('split_planes', False), dtype=spec['dtype'],
+                    loader_procs=spec.get('loader_procs', 0))
 
 
 def _child_main(target, arg, parent_pid):
@@ -397,21 +404,28 @@ def spooled_items(spools):
                 yield json.loads(line), os.path.join(spool, '%d.npy' % n)
 
 
-def create_label_from_model(args, param_dir, iteration, out_dir, out_zip):
-    """labels_from_segnet.save_labels over the first n_labels images of the split, sharded over n_gpus spawned
-    workers -> out_zip"""
+def label_specs(args, param_dir, iteration, out_dir):
+    """the labelling workers' arguments (label_worker): one contiguous range of the first n_labels images per GPU"""
     soft_label = args.use_soft_label or args.use_mse
     same_device = os.environ.get('SPA_BENCH_SAME_DEVICE') == '1'
     spool_root = out_dir + '.spool'
-    os.makedirs(out_dir, exist_ok=True)
     specs = []
     for i, (start, end) in enumerate(label_ranges(args.n_labels, args.n_gpus)):
         specs.append({'device': 0 if same_device else i, 'param_dir': param_dir, 'iteration': iteration,
                       'img_zip_fn': args.img_zip_fn, 'label_zip_fn': args.label_zip_fn, 'out_dir': out_dir,
                       'start': start, 'end': end, 'soft_label': soft_label, 'eval_shape': list(args.eval_shape),
                       'save_each': args.save_each, 'figure': not args.no_figure, 'dtype': args.label_dtype,
-                      'split_planes': args.label_split_planes,
+                      'split_planes': args.label_split_planes, 'loader_procs': args.label_loader_procs,
                       'spool': os.path.join(spool_root, 'w%d' % i)})
+    return specs
+
+
+def create_label_from_model(args, param_dir, iteration, out_dir, out_zip):
+    """labels_from_segnet.save_labels over the first n_labels images of the split, sharded over n_gpus spawned
+    workers -> out_zip"""
+    spool_root = out_dir + '.spool'
+    os.makedirs(out_dir, exist_ok=True)
+    specs = label_specs(args, param_dir, iteration, out_dir)
     run_workers(label_worker, specs, args.child_timeout)
     spools = [s['spool'] for s in specs]
     with open(os.path.join(out_dir, 'result.json'), 'a') as out:
