@@ -1,14 +1,12 @@
 """GPU tests of bf16 SegNet-Basic inference (spa_segnet_encode_bf16 / spa_segnet_decode_bf16, SegNetBasic(dtype='bf16'),
-labels_from_segnet.py --dtype bf16): each of the four layer forms against a float64 restatement on the kernel's own
-bf16 operands, full and bounded writes, determinism across batch positions, the refusals, the whole network at the
-training size against a restatement that rounds every layer's operands to bf16, the fp32 default left as it was, and
-the labelling driver end to end on a synthetic zipped dataset."""
-import ctypes
+labels_from_segnet.py --dtype bf16): each of the four layer forms against the float64 restatement of
+tests/segnet_ref.py on the kernel's own bf16 operands, full and bounded writes, determinism across batch positions,
+the refusals, the whole network at the training size against a restatement that rounds every layer's operands to bf16,
+the fp32 default left as it was, and the labelling driver end to end on a synthetic zipped dataset."""
 import importlib
 import json
 import os
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -18,6 +16,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip('torch')
 F = torch.nn.functional
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import segnet_ref as sref  # noqa: E402
+import segnet_train_synth as syn  # noqa: E402
+from segnet_ref import channels_last, conv7, conv_bias, nchw64, r16, random_params, windows  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 segnet = importlib.import_module('superpixel-align_amd.segnet')
@@ -39,88 +41,18 @@ def eng():
     e.close()
 
 
-def random_params(seed):
-    """Chainer-layout parameters scaled so activations stay O(1) (tests/test_gpu_segnet.py's)."""
-    rng = np.random.default_rng(seed)
-    p = {}
-    for i, name in enumerate(segnet.LAYERS):
-        cin = 3 if i == 0 else 64
-        p[name + '/W'] = (rng.standard_normal((64, cin, 7, 7)) * np.sqrt(2.0 / (cin * 49))).astype(np.float32)
-        p[name + '_bn/gamma'] = rng.uniform(0.5, 1.5, 64).astype(np.float32)
-        p[name + '_bn/beta'] = rng.uniform(-0.2, 0.2, 64).astype(np.float32)
-        p[name + '_bn/avg_mean'] = rng.uniform(-0.2, 0.2, 64).astype(np.float32)
-        p[name + '_bn/avg_var'] = rng.uniform(0.5, 2.0, 64).astype(np.float32)
-    p['conv_classifier/W'] = (rng.standard_normal((2, 64, 1, 1)) / 4).astype(np.float32)
-    p['conv_classifier/b'] = rng.uniform(-0.1, 0.1, 2).astype(np.float32)
-    return p
-
-
-# ------------------------------------------------------------------------------- float64 restatement
-def r16(t):
-    """the bf16 operand of a float32 value, as float64"""
-    return st.bf16_round(torch.as_tensor(t).float()).double()
-
-
 def folded(p, name):
     """(device packed float32 weight, device bias, float64 (64,Cin,7,7) bf16 weight operand, float64 bias)"""
-    w, b = segnet.fold_bn(p)[name]
-    dev = (torch.from_numpy(segnet.pack_weight(w)).cuda(), torch.from_numpy(b).cuda())
-    return dev + (r16(torch.from_numpy(w)), torch.from_numpy(b).double())
-
-
-def conv7(h, w):
-    """float64 7x7 convolution, padding 3, in strips of 64 output rows (bounded im2col memory at 512 x 1024)"""
-    H = h.shape[2]
-    hp = F.pad(h, (0, 0, 3, 3))
-    return torch.cat([F.conv2d(hp[:, :, y0:min(y0 + 64, H) + 6], w, padding=(0, 3)) for y0 in range(0, H, 64)], 2)
-
-
-def windows(h):
-    B, C, H, W = h.shape
-    return h.reshape(B, C, H // 2, 2, W // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, C, H // 2, W // 2, 4)
-
-
-def near_ties(ref, tol):
-    top2 = windows(ref).sort(-1, descending=True).values
-    return (top2[..., 0] - top2[..., 1]) < tol
-
-
-def nchw64(t):
-    """a (B,64,h,w) channels-last device tensor -> float64 CPU (B,64,h,w)"""
-    return t.detach().cpu().double()
+    return sref.folded(p, name, operand=r16)
 
 
 def conv1_operand(eng, img):
-    """conv1's float32 input exactly as the kernels load it (standardised, LRN in float32): the float32 training
-    forward with a centre-tap identity weight returns it (one exact product per output), (B,3,H,W) float32 on the CPU"""
-    wid = torch.zeros((64, 3, 7, 7))
-    for c in range(3):
-        wid[c, c, 3, 3] = 1.0
-    wt = torch.from_numpy(segnet.pack_weight(wid.numpy())).cuda()
-    y, _ = eng.segnet_train_forward(torch.as_tensor(img).cuda().contiguous(), wt, None, segnet.MEAN, segnet.STD,
-                                    stats=False)
-    x1 = y[..., :3].permute(0, 3, 1, 2).cpu().contiguous()
-    del y
-    assert (x1.double() - st.conv1_input(torch.as_tensor(img).double())).abs().max() < 1e-5
-    return x1
+    """conv1's float32 input as the kernels load it, checked against the float64 restatement, (B,3,H,W) on the CPU"""
+    return sref.nchw(sref.conv1_operand(eng, img, check=True)).contiguous()
 
 
-def check_pool(pooled, idx, ref, what):
-    """values within LAYER_TOL max|ref| of the oracle's window maximum; indices equal except where the window's top two
-    oracle values are closer than that (test_gpu_segnet.check_pool's rule)"""
-    tol = LAYER_TOL * float(ref.abs().max())
-    win = windows(ref)
-    yi = win.argmax(-1)
-    yv = win.gather(-1, yi[..., None])[..., 0]
-    err = float((nchw64(pooled) - yv).abs().max())
-    assert err <= tol, '%s: pooled error %.3g > %.3g' % (what, err, tol)
-    bad = (idx.cpu().long() != yi) & ~near_ties(ref, tol)
-    assert int(bad.sum()) == 0, '%s: %d pooling indices differ outside near-ties' % (what, int(bad.sum()))
-    return err / float(ref.abs().max())
-
-
-def channels_last(t):
-    return t.cuda().contiguous(memory_format=torch.channels_last)
+def check_pool(pooled, idx, ref64, what):
+    return sref.check_pool_near_ties(pooled, idx, ref64, LAYER_TOL, what)
 
 
 # ------------------------------------------------------------------------------- the four forms
@@ -139,7 +71,7 @@ def test_conv1_against_float64(eng, shape):
     pooled, idx = eng.segnet_encode_bf16(img.cuda().contiguous(), w, b, segnet.MEAN, segnet.STD)
     torch.cuda.synchronize()
     assert pooled.shape == (B, 64, H // 2, W // 2) and pooled.is_contiguous(memory_format=torch.channels_last)
-    ref = torch.relu(conv7(r16(conv1_operand(eng, img)), w64) + b64[None, :, None, None])
+    ref = torch.relu(conv_bias(r16(conv1_operand(eng, img)), w64, b64))
     e = check_pool(pooled, idx, ref, 'conv1 %s' % (shape,))
     print('conv1 %s: pooled error %.3g of max|ref|' % (shape, e))
 
@@ -153,7 +85,7 @@ def test_encoder_64_against_float64(eng, shape):
     pooled, idx = eng.segnet_encode_bf16(x, w, b)
     torch.cuda.synchronize()
     assert pooled.shape == (B, 64, H // 2, W // 2)
-    ref = torch.relu(conv7(r16(x.cpu()), w64) + b64[None, :, None, None])
+    ref = torch.relu(conv_bias(r16(x.cpu()), w64, b64))
     e = check_pool(pooled, idx, ref, 'encoder %s' % (shape,))
     print('encoder %s: pooled error %.3g of max|ref|' % (shape, e))
 
@@ -175,7 +107,7 @@ def test_decoder_against_float64(eng, shape):
     y = eng.segnet_decode_bf16(h, idx, w, b)
     torch.cuda.synchronize()
     assert y.shape == (B, 64, 2 * Hh, 2 * Wh) and y.is_contiguous(memory_format=torch.channels_last)
-    ref = conv7(st.unpool_ref(r16(h.cpu()), idx.cpu().long()), w64) + b64[None, :, None, None]
+    ref = conv_bias(st.unpool_ref(r16(h.cpu()), idx.cpu().long()), w64, b64)
     e = float((nchw64(y) - ref).abs().max()) / float(ref.abs().max())
     print('decoder %s: error %.3g of max|ref|' % (shape, e))
     assert e <= LAYER_TOL
@@ -191,7 +123,7 @@ def test_decode1_against_float64(eng, shape):
     prob = eng.segnet_decode_bf16(h, idx, w, b, torch.from_numpy(wc).cuda(), torch.from_numpy(bc).cuda())
     torch.cuda.synchronize()
     assert prob.shape == (B, 2, 2 * Hh, 2 * Wh) and prob.is_contiguous()
-    y = conv7(st.unpool_ref(r16(h.cpu()), idx.cpu().long()), w64) + b64[None, :, None, None]
+    y = conv_bias(st.unpool_ref(r16(h.cpu()), idx.cpu().long()), w64, b64)
     z = F.conv2d(y, torch.from_numpy(wc).double()[:, :, None, None], torch.from_numpy(bc).double())
     ref = torch.softmax(z, 1)
     e = float((prob.cpu().double() - ref).abs().max())
@@ -200,129 +132,22 @@ def test_decode1_against_float64(eng, shape):
 
 
 # ------------------------------------------------------------------------------- writes, through the C entry points
-def _poisoned(n, dtype, fill, guard=4096):
-    return torch.full((n + guard,), fill, dtype=dtype, device='cuda')
-
-
 @pytest.mark.parametrize('form', ['conv1', 'enc', 'dec', 'dec1'])
 def test_outputs_fully_written_and_bounded(eng, form):
-    lib, ctx = eng._lib, eng._ctx
-    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
-    p = random_params(38)
-    B, H, W = (2, 48, 80) if form in ('conv1', 'dec1') else (3, 6, 10)
-    g = torch.Generator().manual_seed(39)
-    NHWC, NCHW = 0, 1
-    if form in ('conv1', 'enc'):
-        n = B * (H // 2) * (W // 2) * 64
-        out = _poisoned(n, torch.float32, float('nan'))
-        oi = _poisoned(n, torch.uint8, 255)
-        if form == 'conv1':
-            x = (torch.rand((B, 3, H, W), generator=g) * 255).cuda()
-            w, b, _, _ = folded(p, 'conv1')
-            m = (ctypes.c_float * 3)(*segnet.MEAN)
-            sd = (ctypes.c_float * 3)(*segnet.STD)
-            rc = lib.spa_segnet_encode_bf16(ctx, P(x), NCHW, B, H, W, 3, P(w), P(b), m, sd, P(out), P(oi), s)
-        else:
-            x = torch.randn((B, H, W, 64), generator=g).cuda()
-            w, b, _, _ = folded(p, 'conv2')
-            rc = lib.spa_segnet_encode_bf16(ctx, P(x), NHWC, B, H, W, 64, P(w), P(b), None, None, P(out), P(oi), s)
-        torch.cuda.synchronize()
-        assert rc == 0
-        assert not torch.isnan(out[:n]).any().item(), 'a pooled value was not stored'
-        assert int(oi[:n].max()) <= 3, 'a pooling index was not stored'
-        assert torch.isnan(out[n:]).all().item() and bool((oi[n:] == 255).all()), 'a kernel wrote past its output'
-    else:
-        Hh, Wh = H // 2, W // 2
-        h = torch.rand((B, Hh, Wh, 64), generator=g).cuda()
-        idx = torch.randint(0, 4, (B, Hh, Wh, 64), generator=g, dtype=torch.uint8).cuda()
-        w, b, _, _ = folded(p, 'conv_decode1' if form == 'dec1' else 'conv_decode2')
-        if form == 'dec1':
-            wc, bc = (torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in segnet.fold_bn(p)['conv_classifier'])
-            n = B * 2 * H * W
-        else:
-            wc = bc = None
-            n = B * H * W * 64
-        out = _poisoned(n, torch.float32, float('nan'))
-        rc = lib.spa_segnet_decode_bf16(ctx, P(h), P(idx), NHWC, B, Hh, Wh, P(w), P(b),
-                                        P(wc) if wc is not None else None, P(bc) if bc is not None else None,
-                                        P(out), s)
-        torch.cuda.synchronize()
-        assert rc == 0
-        assert not torch.isnan(out[:n]).any().item(), 'an output was not stored'
-        assert torch.isnan(out[n:]).all().item(), 'a kernel wrote past its output'
+    sref.check_outputs_written(eng, '_bf16', form)
 
 
 # ------------------------------------------------------------------------------- determinism
 def test_determinism_batch_position(eng):
-    p = random_params(40)
-    model = segnet.SegNetBasic(p, engine=eng, dtype='bf16')
     g = np.random.default_rng(41)
+    model = segnet.SegNetBasic(random_params(40), engine=eng, dtype='bf16')
     imgs = torch.from_numpy(g.integers(0, 256, (3, 3, 48, 80)).astype(np.float32)).cuda()
-    one = model.forward(imgs[1:2].contiguous())
-    three = model.forward(imgs)
-    again = model.forward(imgs)
-    torch.cuda.synchronize()
-    assert torch.equal(one[0], three[1])
-    assert torch.equal(three, again)
-    # every layer's output repeats bit for bit too
-    t1, t2 = [], []
-    model.forward(imgs, trace=t1)
-    model.forward(imgs, trace=t2)
-    for (a, ai), (b, bi) in zip(t1, t2):
-        assert torch.equal(a, b) and torch.equal(ai, bi)
+    sref.check_batch_position(model, imgs, layers=True)             # every layer's output repeats bit for bit too
 
 
 # ------------------------------------------------------------------------------- refusals
 def test_refusals_launch_nothing(eng):
-    lib, ctx = eng._lib, eng._ctx
-    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
-    x3 = torch.zeros((1, 3, 48, 48), device='cuda')
-    x64 = torch.zeros((1, 64, 32, 32), device='cuda')
-    w3 = torch.zeros((49, 64, 4), device='cuda')
-    w64 = torch.zeros((49, 64, 64), device='cuda')
-    b = torch.zeros(64, device='cuda')
-    pooled = torch.full((1 << 18,), float('nan'), device='cuda')
-    idx = torch.full((1 << 18,), 9, dtype=torch.uint8, device='cuda')
-    m = (ctypes.c_float * 3)(*segnet.MEAN)
-    sd = (ctypes.c_float * 3)(*segnet.STD)
-    NHWC, NCHW = 0, 1
-    enc, dec = lib.spa_segnet_encode_bf16, lib.spa_segnet_decode_bf16
-    cases = [
-        # conv1 at H = 40 (not a multiple of 16)
-        (enc(ctx, P(x3), NCHW, 1, 40, 48, 3, P(w3), P(b), m, sd, P(pooled), P(idx), s), -1),
-        # a 64-channel stage at an odd width
-        (enc(ctx, P(x64), NHWC, 1, 32, 31, 64, P(w64), P(b), None, None, P(pooled), P(idx), s), -1),
-        # Cin 16
-        (enc(ctx, P(x64), NHWC, 1, 32, 32, 16, P(w64), P(b), None, None, P(pooled), P(idx), s), -1),
-        # 64 channels stored planar
-        (enc(ctx, P(x64), NCHW, 1, 32, 32, 64, P(w64), P(b), None, None, P(pooled), P(idx), s), -4),
-        # conv1 image stored channels-last
-        (enc(ctx, P(x3), NHWC, 1, 48, 48, 3, P(w3), P(b), m, sd, P(pooled), P(idx), s), -4),
-        # decoder input stored planar
-        (dec(ctx, P(x64), P(idx), NCHW, 1, 16, 16, P(w64), P(b), None, None, P(pooled), s), -4),
-        # decode1 output 2 x (20, 20) = (40, 40): not a multiple of 16
-        (dec(ctx, P(x64), P(idx), NHWC, 1, 20, 20, P(w64), P(b), P(b), P(b), P(pooled), s), -1),
-    ]
-    # the float32 stages refuse the same calls with the same codes
-    want = [
-        lib.spa_segnet_encode(ctx, P(x3), NCHW, 1, 40, 48, 3, P(w3), P(b), m, sd, P(pooled), P(idx), s),
-        lib.spa_segnet_encode(ctx, P(x64), NHWC, 1, 32, 31, 64, P(w64), P(b), None, None, P(pooled), P(idx), s),
-        lib.spa_segnet_encode(ctx, P(x64), NHWC, 1, 32, 32, 16, P(w64), P(b), None, None, P(pooled), P(idx), s),
-        lib.spa_segnet_encode(ctx, P(x64), NCHW, 1, 32, 32, 64, P(w64), P(b), None, None, P(pooled), P(idx), s),
-        lib.spa_segnet_encode(ctx, P(x3), NHWC, 1, 48, 48, 3, P(w3), P(b), m, sd, P(pooled), P(idx), s),
-        lib.spa_segnet_decode(ctx, P(x64), P(idx), NCHW, 1, 16, 16, P(w64), P(b), None, None, P(pooled), s),
-        lib.spa_segnet_decode(ctx, P(x64), P(idx), NHWC, 1, 20, 20, P(w64), P(b), P(b), P(b), P(pooled), s),
-    ]
-    torch.cuda.synchronize()
-    assert [rc for rc, _ in cases] == [w for _, w in cases]
-    assert [rc for rc, _ in cases] == want
-    assert torch.isnan(pooled).all().item() and bool((idx == 9).all())         # nothing was written
-    with pytest.raises(Exception, match='-4'):
-        eng.segnet_encode_bf16(torch.zeros((1, 64, 32, 32), device='cuda'), w64, b)
-    with pytest.raises(Exception, match='-1'):
-        eng.segnet_encode_bf16(torch.zeros((1, 3, 40, 48), device='cuda'), w3, b, segnet.MEAN, segnet.STD)
+    sref.check_inference_refusals(eng, '_bf16')
 
 
 # ------------------------------------------------------------------------------- whole network
@@ -376,7 +201,7 @@ def test_predict_full_size(eng):
     # 1. every layer at full size against float64 on the bf16 operands of the device's own input to it
     f = segnet.fold_bn(p)
     _, _, w64, b64 = folded(p, 'conv1')
-    ref = torch.relu(conv7(r16(conv1_operand(eng, torch.from_numpy(img))), w64) + b64[None, :, None, None])
+    ref = torch.relu(conv_bias(r16(conv1_operand(eng, torch.from_numpy(img))), w64, b64))
     err = (nchw64(trace[0][0]) - windows(ref).max(-1).values).abs() / float(ref.abs().max())
     flips = float((err > LAYER_TOL).double().mean())
     print('conv1 at full size: %.3g of the outputs beyond LAYER_TOL, worst %.3g of max|ref|' % (flips, float(err.max())))
@@ -385,12 +210,12 @@ def test_predict_full_size(eng):
     worst = 0.0
     for name, (pooled, idx), (h, _) in zip(segnet.ENCODERS[1:], trace[1:], trace):
         _, _, w64, b64 = folded(p, name)
-        ref = torch.relu(conv7(r16(h.cpu()), w64) + b64[None, :, None, None])
+        ref = torch.relu(conv_bias(r16(h.cpu()), w64, b64))
         worst = max(worst, check_pool(pooled, idx, ref, name))
     hd = trace[-1][0]
     for name, (_, idx) in zip(segnet.DECODERS, trace[::-1]):
         w, b, w64, b64 = folded(p, name)
-        ref = conv7(st.unpool_ref(r16(hd.cpu()), idx.cpu().long()), w64) + b64[None, :, None, None]
+        ref = conv_bias(st.unpool_ref(r16(hd.cpu()), idx.cpu().long()), w64, b64)
         if name == 'conv_decode1':
             wc, bc = f['conv_classifier']
             hd = eng.segnet_decode_bf16(hd, idx, w, b, torch.from_numpy(wc).cuda(), torch.from_numpy(bc).cuda())
@@ -444,12 +269,6 @@ REF_KEYS = ['img_fn', 'label_fn', 'road_iou', 'non_road_iou', 'precision', 'reca
             'eval_shape', 'save_each', 'train_args']
 
 
-def _run(args, cwd):
-    r = subprocess.run([sys.executable] + args, cwd=cwd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return r
-
-
 def _files(d):
     out = {}
     for fn in sorted(os.listdir(d)):
@@ -459,21 +278,16 @@ def _files(d):
 
 
 def test_train_then_label_bf16_end_to_end(tmp_path):
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import segnet_train_synth as syn
     z = syn.write(str(tmp_path / 'data'), 8, 3, 64, 128)
-    common = ['--train_img_zip', z[0], '--train_label_zip', z[1], '--val_img_zip', z[2], '--val_label_zip', z[3],
-              '--batchsize', '2', '--input_shape', '64', '128', '--eval_shape', '64', '128',
-              '--train_limit', str(E2E_ITERS), 'iteration', '--val_interval', '20', 'iteration',
-              '--log_interval', '10', 'iteration', '--decay_iteration', '30']
+    common = syn.train_args(z, E2E_ITERS, 20, 10, extra=['--decay_iteration', '30'])
     d1 = str(tmp_path / 'run')
-    _run([os.path.join(ROOT, 'train_segnet.py')] + common + ['--result_dir', d1], ROOT)
+    syn.run_python([os.path.join(ROOT, 'train_segnet.py')] + common + ['--result_dir', d1], ROOT)
     label_cmd = [os.path.join(ROOT, 'labels_from_segnet.py'), '--param_dir', d1, '--iteration', str(E2E_ITERS),
                  '--img_zip_fn', z[2], '--label_zip_fn', z[3], '--start_index', '0', '--end_index', '3',
                  '--eval_shape', '64', '128', '--no_figure']
     out_b, out_f = str(tmp_path / 'labels_bf16'), str(tmp_path / 'labels')
-    _run(label_cmd + ['--out_dir', out_b, '--dtype', 'bf16'], ROOT)
-    _run(label_cmd + ['--out_dir', out_f], ROOT)
+    syn.run_python(label_cmd + ['--out_dir', out_b, '--dtype', 'bf16'], ROOT)
+    syn.run_python(label_cmd + ['--out_dir', out_f], ROOT)
     lines = [json.loads(l) for l in open(os.path.join(out_b, 'result.json')) if l.strip()]
     assert len(lines) == 3
     TP = FP = FN = 0
@@ -507,5 +321,5 @@ def test_train_then_label_bf16_end_to_end(tmp_path):
             assert np.array_equal(res[k[:-len('_scores')]], np.argmax(v, 0).astype(bool))
     # the float32 run with an explicit --dtype fp32 writes the same bytes as without it
     shutil.move(out_f, out_f + '_default')
-    _run(label_cmd + ['--out_dir', out_f, '--dtype', 'fp32'], ROOT)
+    syn.run_python(label_cmd + ['--out_dir', out_f, '--dtype', 'fp32'], ROOT)
     assert _files(out_f) == _files(out_f + '_default')

@@ -10,7 +10,6 @@ import importlib
 import io
 import json
 import os
-import socket
 import subprocess
 import sys
 import zipfile
@@ -25,33 +24,22 @@ torch = pytest.importorskip('torch')
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import segnet_train_synth as syn  # noqa: E402
+
 st = importlib.import_module('superpixel-align_amd.segnet_train')
 
 TIMEOUT = 900
 SHARED = {'SPA_DIST_BACKEND': 'gloo', 'SPA_BENCH_SAME_DEVICE': '1'}
 
 
-def _port():
-    with socket.socket() as s:
-        s.bind(('127.0.0.1', 0))
-        return s.getsockname()[1]
-
-
-def _env(**kw):
-    env = {k: v for k, v in os.environ.items()
-           if k not in ('SPA_DIST_FORCE', 'SPA_DIST_BACKEND', 'SPA_BENCH_SAME_DEVICE', 'RANK', 'WORLD_SIZE',
-                        'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
-    env.update(kw)
-    return env
-
-
 def _ranks(script, args, n, env_extra, tmp_path):
     """n processes of `script` as ranks 0..n-1 of one gloo group; every one must exit with 0"""
-    port = str(_port())
+    port = str(syn.free_port())
     procs = []
     for r in range(n):
-        env = _env(RANK=str(r), WORLD_SIZE=str(n), LOCAL_RANK=str(r), MASTER_ADDR='127.0.0.1', MASTER_PORT=port,
-                   **env_extra)
+        env = syn.env(RANK=str(r), WORLD_SIZE=str(n), LOCAL_RANK=str(r), MASTER_ADDR='127.0.0.1', MASTER_PORT=port,
+                      **env_extra)
         procs.append(subprocess.Popen([sys.executable, '-c', script] + args, env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.STDOUT))
     outs = []
@@ -166,38 +154,21 @@ def test_two_rank_step_against_float64(tmp_path, dtype):
 
 # ------------------------------------------------------------------------------- train_segnet.py
 def _synth(tmp_path, n_train=8, n_val=3):
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import segnet_train_synth as syn
     return syn.write(str(tmp_path / 'data'), n_train, n_val, 64, 128)
 
 
 def _common(z, iters, every):
-    return ['--train_img_zip', z[0], '--train_label_zip', z[1], '--val_img_zip', z[2], '--val_label_zip', z[3],
-            '--batchsize', '2', '--input_shape', '64', '128', '--eval_shape', '64', '128', '--random',
-            '--train_limit', str(iters), 'iteration', '--val_interval', str(every), 'iteration',
-            '--log_interval', str(every), 'iteration']
+    return syn.train_args(z, iters, every, every, extra=['--random'])
 
 
 def _run(cmd, env, ok=True):
-    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=TIMEOUT)
-    if ok:
-        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return r
+    return syn.run(cmd, env, ROOT, TIMEOUT, ok)
 
 
 def _torchrun(n, argv, env):
     return [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n),
-            '--master-addr', '127.0.0.1', '--master-port', str(_port()), os.path.join(ROOT, 'train_segnet.py')] + argv
-
-
-def _same_snapshot(fa, fb, keys=None):
-    with np.load(fa) as a, np.load(fb) as b:
-        ks = set(a.files) & set(b.files) if keys == 'common' else set(a.files)
-        if keys != 'common':
-            assert set(a.files) == set(b.files)
-        for k in ks:
-            assert np.array_equal(a[k], b[k]) and a[k].dtype == b[k].dtype, k
-        return ks
+            '--master-addr', '127.0.0.1', '--master-port', str(syn.free_port()),
+            os.path.join(ROOT, 'train_segnet.py')] + argv
 
 
 def test_rccl_one_rank_matches_one_process(tmp_path):
@@ -205,11 +176,11 @@ def test_rccl_one_rank_matches_one_process(tmp_path):
     common = _common(z, 4, 2)
     d1, d2 = str(tmp_path / 'single'), str(tmp_path / 'rccl')
     script = os.path.join(ROOT, 'train_segnet.py')
-    _run([sys.executable, script] + common + ['--result_dir', d1], _env())
+    _run([sys.executable, script] + common + ['--result_dir', d1], syn.env())
     _run([sys.executable, script, '--data_parallel'] + common + ['--result_dir', d2],
-         _env(SPA_DIST_FORCE='1', RANK='0', WORLD_SIZE='1', LOCAL_RANK='0', MASTER_ADDR='127.0.0.1',
-              MASTER_PORT=str(_port())))
-    keys = _same_snapshot(os.path.join(d1, 'snapshot_iter_4'), os.path.join(d2, 'snapshot_iter_4'), 'common')
+         syn.env(SPA_DIST_FORCE='1', RANK='0', WORLD_SIZE='1', LOCAL_RANK='0', MASTER_ADDR='127.0.0.1',
+                 MASTER_PORT=str(syn.free_port())))
+    keys = syn.same_snapshot(os.path.join(d1, 'snapshot_iter_4'), os.path.join(d2, 'snapshot_iter_4'), 'common')
     assert len(keys) > 60
     assert st.snapshot_world_size(os.path.join(d2, 'snapshot_iter_4')) == 1
     args = json.load(open(os.path.join(d2, 'args.txt')))
@@ -222,7 +193,7 @@ def test_rccl_one_rank_matches_one_process(tmp_path):
 
 def test_torchrun_two_ranks_resume_and_refusal(tmp_path):
     z = _synth(tmp_path)
-    env = _env(**SHARED)
+    env = syn.env(**SHARED)
     runs = tmp_path / 'runs'
     da, db, dc = str(runs / 'straight'), str(runs / 'resumed'), str(runs / 'refused')
     _run(_torchrun(2, ['--data_parallel'] + _common(z, 4, 2) + ['--result_dir', da], env), env)
@@ -239,7 +210,7 @@ def test_torchrun_two_ranks_resume_and_refusal(tmp_path):
     # 2 steps + --resume + 2 steps == 4 steps, bit for bit
     _run(_torchrun(2, ['--data_parallel'] + _common(z, 4, 2) +
                    ['--result_dir', db, '--resume', os.path.join(da, 'snapshot_iter_2')], env), env)
-    _same_snapshot(os.path.join(da, 'snapshot_iter_4'), os.path.join(db, 'snapshot_iter_4'))
+    syn.same_snapshot(os.path.join(da, 'snapshot_iter_4'), os.path.join(db, 'snapshot_iter_4'))
     # another world size is refused
     r = _run(_torchrun(1, ['--data_parallel'] + _common(z, 4, 2) +
                        ['--result_dir', dc, '--resume', os.path.join(da, 'snapshot_iter_2')], env), env, ok=False)
@@ -272,7 +243,7 @@ def test_run_train_rounds_two_rounds(tmp_path):
            '--img_zip_fn', z[0], '--label_zip_fn', gt, '--estimated_label_zip_fn', z[1],
            '--val_img_zip', z[2], '--val_label_zip', z[3],
            '--result_base_dir', base, '--no_figure', '--child_timeout', str(TIMEOUT)]
-    r = subprocess.run(cmd, cwd=str(tmp_path), env=_env(**SHARED), capture_output=True, text=True,
+    r = subprocess.run(cmd, cwd=str(tmp_path), env=syn.env(**SHARED), capture_output=True, text=True,
                        timeout=3 * TIMEOUT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     firsts = glob.glob(os.path.join(base, 'train_round1_*'))
@@ -315,7 +286,7 @@ def test_run_train_rounds_stops_at_failing_child(tmp_path):
            '--img_zip_fn', str(tmp_path / 'missing.zip'),
            '--label_zip_fn', z[1], '--estimated_label_zip_fn', z[1], '--val_img_zip', z[2], '--val_label_zip', z[3],
            '--result_base_dir', base, '--no_figure', '--child_timeout', str(TIMEOUT)]
-    r = subprocess.run(cmd, cwd=str(tmp_path), env=_env(**SHARED), capture_output=True, text=True, timeout=TIMEOUT)
+    r = subprocess.run(cmd, cwd=str(tmp_path), env=syn.env(**SHARED), capture_output=True, text=True, timeout=TIMEOUT)
     assert r.returncode != 0
     assert 'no further process is started' in r.stderr
     first = glob.glob(os.path.join(base, 'train_round1_*'))

@@ -1,10 +1,9 @@
 """GPU tests of split-plane SegNet-Basic inference (spa_segnet_encode_f16x3 / spa_segnet_decode_f16x3,
 SegNetBasic(split_planes=True), labels_from_segnet.py --split_planes, train_segnet.py --val_split_planes): float32
 accuracy on the f16 matrix cores.  The reference is float64 on the UNROUNDED float32 operands (the oracle functions of
-tests/test_gpu_segnet.py, restated here) and the bounds are that file's float32-inference bounds: the mode claims
+tests/segnet_ref.py) and the bounds are tests/test_gpu_segnet.py's float32-inference bounds: the mode claims
 float32 accuracy, so it is held to what the float32 kernels are held to.  Every layer test prints this mode's worst
 error beside the float32 kernel's on the same inputs."""
-import ctypes
 import importlib
 import json
 import os
@@ -18,6 +17,11 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip('torch')
 F = torch.nn.functional
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import segnet_ref as sref  # noqa: E402
+import segnet_train_synth as syn  # noqa: E402
+from segnet_ref import (channels_last, classifier, conv_bias, folded, lrn_chainer, nchw64, pool_err,  # noqa: E402
+                        random_params, standardise, t64, unpool)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 segnet = importlib.import_module('superpixel-align_amd.segnet')
@@ -47,115 +51,8 @@ def eng():
     e.close()
 
 
-def random_params(seed):
-    """Chainer-layout parameters scaled so activations stay O(1) (tests/test_gpu_segnet.py's)."""
-    rng = np.random.default_rng(seed)
-    p = {}
-    for i, name in enumerate(segnet.LAYERS):
-        cin = 3 if i == 0 else 64
-        p[name + '/W'] = (rng.standard_normal((64, cin, 7, 7)) * np.sqrt(2.0 / (cin * 49))).astype(np.float32)
-        p[name + '_bn/gamma'] = rng.uniform(0.5, 1.5, 64).astype(np.float32)
-        p[name + '_bn/beta'] = rng.uniform(-0.2, 0.2, 64).astype(np.float32)
-        p[name + '_bn/avg_mean'] = rng.uniform(-0.2, 0.2, 64).astype(np.float32)
-        p[name + '_bn/avg_var'] = rng.uniform(0.5, 2.0, 64).astype(np.float32)
-    p['conv_classifier/W'] = (rng.standard_normal((2, 64, 1, 1)) / 4).astype(np.float32)
-    p['conv_classifier/b'] = rng.uniform(-0.1, 0.1, 2).astype(np.float32)
-    return p
-
-
-# ------------------------------------------------------------------------------- float64 oracle
-def t64(a):
-    return torch.as_tensor(np.asarray(a), dtype=torch.float64)
-
-
-def standardise(x):
-    """the dataset's two float32 operations on the 0..255 image"""
-    x = np.asarray(x, np.float32).copy()
-    x -= segnet.MEAN[None, :, None, None]
-    x /= segnet.STD[None, :, None, None]
-    return x
-
-
-def lrn_chainer(x):
-    s = (x * x).sum(1, keepdim=True)                 # n = 5 covers all three channels
-    return x * (1.0 + 1e-4 / 5 * s) ** -0.75
-
-
-def conv7(h, w):
-    """float64 7x7 convolution, padding 3, in strips of 64 output rows (bounded im2col memory at 512 x 1024)"""
-    H = h.shape[2]
-    hp = F.pad(h, (0, 0, 3, 3))
-    return torch.cat([F.conv2d(hp[:, :, y0:min(y0 + 64, H) + 6], w, padding=(0, 3)) for y0 in range(0, H, 64)], 2)
-
-
-def windows(h):
-    B, C, H, W = h.shape
-    return h.reshape(B, C, H // 2, 2, W // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, C, H // 2, W // 2, 4)
-
-
-def unpool(h, idx):
-    B, C, h2, w2 = h.shape
-    out = torch.zeros(B, C, h2, w2, 4, dtype=torch.float64)
-    out.scatter_(-1, idx.long()[..., None], h[..., None])
-    return out.reshape(B, C, h2, w2, 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, C, 2 * h2, 2 * w2)
-
-
-def nchw64(t):
-    return t.detach().cpu().double()
-
-
-def channels_last(t):
-    return t.cuda().contiguous(memory_format=torch.channels_last)
-
-
-def folded(p, name, ws=1.0, bs=1.0):
-    """the layer's folded float32 weight and bias, scaled by the powers of two ws / bs (exact) ->
-    (device packed weight, device bias, float64 (64,Cin,7,7) weight, float64 bias)"""
-    w, b = segnet.fold_bn(p)[name]
-    w = (w * np.float32(ws)).astype(np.float32)
-    b = (b * np.float32(bs)).astype(np.float32)
-    return (torch.from_numpy(segnet.pack_weight(w)).cuda(), torch.from_numpy(b).cuda(), t64(w), t64(b))
-
-
-def classifier(p, ws=1.0):
-    wc, bc = segnet.fold_bn(p)['conv_classifier']
-    wc = np.ascontiguousarray(wc * np.float32(ws)).astype(np.float32)
-    return torch.from_numpy(wc).cuda(), torch.from_numpy(bc).cuda(), t64(wc), t64(bc)
-
-
-def decided_windows(v, tol):
-    """v the float64 pre-ReLU output.  A window is decided if all four v <= -tol (index 0, value exactly 0) or if its
-    maximum is >= tol and leads the runner-up by >= tol (index = argmax).  -> (all-negative mask, leader mask, argmax)"""
-    win = windows(v)
-    srt = win.sort(-1, descending=True).values
-    neg = (win <= -tol).all(-1)
-    lead = (srt[..., 0] >= tol) & (srt[..., 0] - srt[..., 1] >= tol)
-    return neg, lead, win.argmax(-1)
-
-
 def check_pool(pooled, idx, v, what):
-    """pooled within LAYER_TOL max|relu(v)| of the window maximum of relu(v) everywhere; the index of every decided
-    window as decided_windows says; the undecided share capped.  -> the value error as a fraction of max|relu(v)|"""
-    ref = torch.relu(v)
-    scale = float(ref.abs().max())
-    tol = LAYER_TOL * scale
-    err = float((nchw64(pooled) - windows(ref).max(-1).values).abs().max())
-    neg, lead, arg = decided_windows(v, tol)
-    exempt = 1.0 - float((neg | lead).double().mean())
-    print('%s: pooled error %.3g of max|ref|, undecided windows %.3g' % (what, err / scale, exempt))
-    assert err <= tol, '%s: pooled error %.3g > %.3g' % (what, err, tol)
-    assert exempt <= EXEMPT_WINDOWS, '%s: %.3g of the windows are undecided' % (what, exempt)
-    di = idx.cpu().long()
-    assert int((di[neg] != 0).sum()) == 0, '%s: an all-negative window has a non-zero index' % what
-    assert bool((pooled.cpu()[neg] == 0.0).all()), '%s: an all-negative window is not exactly 0' % what
-    bad = int((di[lead] != arg[lead]).sum())
-    assert bad == 0, '%s: %d decided pooling indices differ' % (what, bad)
-    return err / scale
-
-
-def pool_err(pooled, v):
-    ref = torch.relu(v)
-    return float((nchw64(pooled) - windows(ref).max(-1).values).abs().max()) / float(ref.abs().max())
+    return sref.check_pool_decided(pooled, idx, v, LAYER_TOL, EXEMPT_WINDOWS, what)
 
 
 def report(what, e3, e32):
@@ -174,7 +71,7 @@ def run_conv1(eng, img, p, ws=1.0, what='conv1'):
     B, _, H, W = img.shape
     assert pooled.shape == (B, 64, H // 2, W // 2) and pooled.is_contiguous(memory_format=torch.channels_last)
     assert idx.dtype == torch.uint8 and idx.shape == pooled.shape
-    v = conv7(lrn_chainer(t64(standardise(img))), w64) + b64[None, :, None, None]
+    v = conv_bias(lrn_chainer(t64(standardise(img))), w64, b64)
     e = check_pool(pooled, idx, v, what)
     report(what, e, pool_err(p32, v))
     return e
@@ -187,7 +84,7 @@ def run_encoder(eng, x, p, xs=1.0, ws=1.0, what='encoder'):
     pooled, idx = eng.segnet_encode_f16x3(xd, w, b)
     p32, _ = eng.segnet_encode(xd, w, b)
     torch.cuda.synchronize()
-    v = conv7(nchw64(xd), w64) + b64[None, :, None, None]
+    v = conv_bias(nchw64(xd), w64, b64)
     e = check_pool(pooled, idx, v, what)
     report(what, e, pool_err(p32, v))
     return e
@@ -208,7 +105,7 @@ def run_decoder(eng, p, xs=1.0, ws=1.0, what='decoder'):
     y32 = eng.segnet_decode(pooled, idx, w, b)
     torch.cuda.synchronize()
     assert y.shape == (2, 64, 32, 64) and y.is_contiguous(memory_format=torch.channels_last)
-    ref = conv7(unpool(nchw64(pooled), idx.cpu()), w64) + b64[None, :, None, None]
+    ref = conv_bias(unpool(nchw64(pooled), idx.cpu()), w64, b64)
     scale = float(ref.abs().max())
     e, e32 = float((nchw64(y) - ref).abs().max()) / scale, float((nchw64(y32) - ref).abs().max()) / scale
     report(what, e, e32)
@@ -226,7 +123,7 @@ def run_decode1(eng, p, xs=1.0, ws=1.0, what='decode1'):
     p32 = eng.segnet_decode(pooled, idx, w, b, wc, bc)
     torch.cuda.synchronize()
     assert prob.shape == (2, 2, 32, 48) and prob.is_contiguous()
-    y = conv7(unpool(nchw64(pooled), idx.cpu()), w64) + b64[None, :, None, None]
+    y = conv_bias(unpool(nchw64(pooled), idx.cpu()), w64, b64)
     ref = torch.softmax(F.conv2d(y, wc64[:, :, None, None], bc64), 1)
     e, e32 = float((nchw64(prob) - ref).abs().max()), float((nchw64(p32) - ref).abs().max())
     report(what + ' probabilities', e, e32)
@@ -307,58 +204,9 @@ def test_all_zero_operands_give_exact_results(eng):
 
 
 # ------------------------------------------------------------------------------- writes, through the C entry points
-def _poisoned(n, dtype, fill, guard=4096):
-    return torch.full((n + guard,), fill, dtype=dtype, device='cuda')
-
-
 @pytest.mark.parametrize('form', ['conv1', 'enc', 'dec', 'dec1'])
 def test_outputs_fully_written_and_bounded(eng, form):
-    """(48, 80) and (6, 10) do not fill the 8 x 32 tiles: ragged right and bottom edges"""
-    lib, ctx = eng._lib, eng._ctx
-    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
-    p = random_params(38)
-    B, H, W = (2, 48, 80) if form in ('conv1', 'dec1') else (3, 6, 10)
-    g = torch.Generator().manual_seed(39)
-    NHWC, NCHW = 0, 1
-    if form in ('conv1', 'enc'):
-        n = B * (H // 2) * (W // 2) * 64
-        out = _poisoned(n, torch.float32, float('nan'))
-        oi = _poisoned(n, torch.uint8, 255)
-        if form == 'conv1':
-            x = (torch.rand((B, 3, H, W), generator=g) * 255).cuda()
-            w, b, _, _ = folded(p, 'conv1')
-            m = (ctypes.c_float * 3)(*segnet.MEAN)
-            sd = (ctypes.c_float * 3)(*segnet.STD)
-            rc = lib.spa_segnet_encode_f16x3(ctx, P(x), NCHW, B, H, W, 3, P(w), P(b), m, sd, P(out), P(oi), s)
-        else:
-            x = torch.randn((B, H, W, 64), generator=g).cuda()
-            w, b, _, _ = folded(p, 'conv2')
-            rc = lib.spa_segnet_encode_f16x3(ctx, P(x), NHWC, B, H, W, 64, P(w), P(b), None, None, P(out), P(oi), s)
-        torch.cuda.synchronize()
-        assert rc == 0
-        assert not torch.isnan(out[:n]).any().item(), 'a pooled value was not stored'
-        assert int(oi[:n].max()) <= 3, 'a pooling index was not stored'
-        assert torch.isnan(out[n:]).all().item() and bool((oi[n:] == 255).all()), 'a kernel wrote past its output'
-    else:
-        Hh, Wh = H // 2, W // 2
-        h = torch.rand((B, Hh, Wh, 64), generator=g).cuda()
-        idx = torch.randint(0, 4, (B, Hh, Wh, 64), generator=g, dtype=torch.uint8).cuda()
-        w, b, _, _ = folded(p, 'conv_decode1' if form == 'dec1' else 'conv_decode2')
-        if form == 'dec1':
-            wc, bc, _, _ = classifier(p)
-            n = B * 2 * H * W
-        else:
-            wc = bc = None
-            n = B * H * W * 64
-        out = _poisoned(n, torch.float32, float('nan'))
-        rc = lib.spa_segnet_decode_f16x3(ctx, P(h), P(idx), NHWC, B, Hh, Wh, P(w), P(b),
-                                         P(wc) if wc is not None else None, P(bc) if bc is not None else None,
-                                         P(out), s)
-        torch.cuda.synchronize()
-        assert rc == 0
-        assert not torch.isnan(out[:n]).any().item(), 'an output was not stored'
-        assert torch.isnan(out[n:]).all().item(), 'a kernel wrote past its output'
+    sref.check_outputs_written(eng, '_f16x3', form)
 
 
 # ------------------------------------------------------------------------------- determinism
@@ -435,80 +283,10 @@ def test_determinism_batch_position(eng):
 
 # ------------------------------------------------------------------------------- refusals
 def test_refusals_launch_nothing(eng):
-    lib, ctx = eng._lib, eng._ctx
-    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
-    x3 = torch.zeros((1, 3, 48, 48), device='cuda')
-    x64 = torch.zeros((1, 64, 32, 32), device='cuda')
-    w3 = torch.zeros((49, 64, 4), device='cuda')
-    w64 = torch.zeros((49, 64, 64), device='cuda')
-    b = torch.zeros(64, device='cuda')
-    pooled = torch.full((1 << 18,), float('nan'), device='cuda')
-    idx = torch.full((1 << 18,), 9, dtype=torch.uint8, device='cuda')
-    m = (ctypes.c_float * 3)(*segnet.MEAN)
-    sd = (ctypes.c_float * 3)(*segnet.STD)
-    NHWC, NCHW = 0, 1
-
-    def table(enc, dec):
-        return [
-            # conv1 at H = 40 (not a multiple of 16)
-            enc(ctx, P(x3), NCHW, 1, 40, 48, 3, P(w3), P(b), m, sd, P(pooled), P(idx), s),
-            # a 64-channel stage at an odd width
-            enc(ctx, P(x64), NHWC, 1, 32, 31, 64, P(w64), P(b), None, None, P(pooled), P(idx), s),
-            # Cin 16
-            enc(ctx, P(x64), NHWC, 1, 32, 32, 16, P(w64), P(b), None, None, P(pooled), P(idx), s),
-            # 64 channels stored planar
-            enc(ctx, P(x64), NCHW, 1, 32, 32, 64, P(w64), P(b), None, None, P(pooled), P(idx), s),
-            # conv1 image stored channels-last
-            enc(ctx, P(x3), NHWC, 1, 48, 48, 3, P(w3), P(b), m, sd, P(pooled), P(idx), s),
-            # decoder input stored planar
-            dec(ctx, P(x64), P(idx), NCHW, 1, 16, 16, P(w64), P(b), None, None, P(pooled), s),
-            # decode1 output 2 x (20, 20) = (40, 40): not a multiple of 16
-            dec(ctx, P(x64), P(idx), NHWC, 1, 20, 20, P(w64), P(b), P(b), P(b), P(pooled), s),
-        ]
-
-    got = table(lib.spa_segnet_encode_f16x3, lib.spa_segnet_decode_f16x3)
-    want = table(lib.spa_segnet_encode, lib.spa_segnet_decode)
-    torch.cuda.synchronize()
-    assert want == [-1, -1, -1, -4, -4, -4, -1]
-    assert got == want
-    assert torch.isnan(pooled).all().item() and bool((idx == 9).all())         # nothing was written
-    with pytest.raises(Exception, match='-4'):
-        eng.segnet_encode_f16x3(torch.zeros((1, 64, 32, 32), device='cuda'), w64, b)
-    with pytest.raises(Exception, match='-1'):
-        eng.segnet_encode_f16x3(torch.zeros((1, 3, 40, 48), device='cuda'), w3, b, segnet.MEAN, segnet.STD)
+    sref.check_inference_refusals(eng, '_f16x3')
 
 
 # ------------------------------------------------------------------------------- whole network
-def bn_conv(p, name, h):
-    y = conv7(h, t64(p[name + '/W']))
-    g, be, mu, var = (t64(p['%s_bn/%s' % (name, k)])[None, :, None, None] for k in segnet.BN_PARAMS)
-    return g * (y - mu) / torch.sqrt(var + segnet.BN_EPS) + be
-
-
-def forward64(p, img, dev_idx):
-    """img (B,3,H,W) 0..255 -> float64 probabilities (B,2,H,W) (tests/test_gpu_segnet.py's forward64).  The device's
-    pooling indices are required to be decided_windows' in every decided window and taken as they are in the others (a
-    near-tie either side may resolve differently; an unpooled value in the other position of its block is an O(1)
-    change)."""
-    h = lrn_chainer(t64(standardise(img)))
-    idxs = []
-    for li, name in enumerate(segnet.ENCODERS):
-        v = bn_conv(p, name, h)
-        y = torch.relu(v)
-        neg, lead, arg = decided_windows(v, 1e-5 * float(y.abs().max()))
-        d = dev_idx[li].cpu().long()
-        assert int((d[neg] != 0).sum()) == 0 and int((d[lead] != arg[lead]).sum()) == 0, name
-        print('%s at full size: undecided windows %.3g' % (name, 1.0 - float((neg | lead).double().mean())))
-        h = windows(y).gather(-1, d[..., None])[..., 0]
-        idxs.append(d)
-        del v, y
-    for name, i in zip(segnet.DECODERS, idxs[::-1]):
-        h = bn_conv(p, name, unpool(h, i))
-    z = F.conv2d(h, t64(p['conv_classifier/W']), t64(p['conv_classifier/b']))
-    return torch.softmax(z, 1)
-
-
 def test_predict_full_size(eng):
     p = random_params(19)
     g = np.random.default_rng(20)
@@ -518,7 +296,8 @@ def test_predict_full_size(eng):
     out32 = segnet.SegNetBasic(p, pred_shape=(1024, 2048), engine=eng).predict(img)
     trace = []
     model.forward(torch.from_numpy(img).cuda(), trace=trace)         # the same launches: the indices predict used
-    ref = forward64(p, img, [i for _, i in trace]).numpy()
+    # the device's pooling indices are required to be decided_windows' (LAYER_TOL max|y|) in every decided window
+    ref = sref.forward64(p, t64(standardise(img)), [i for _, i in trace], sref.decided_indices, LAYER_TOL)[0].numpy()
     for bi in range(2):
         label, score = out[bi]
         assert label.shape == (1024, 2048) and score.shape == (2, 1024, 2048) and score.dtype == np.float32
@@ -580,23 +359,12 @@ REF_KEYS = ['img_fn', 'label_fn', 'road_iou', 'non_road_iou', 'precision', 'reca
             'eval_shape', 'save_each', 'train_args']
 
 
-def _run(args, cwd):
-    r = subprocess.run([sys.executable] + args, cwd=cwd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return r
-
-
 def test_train_then_label_split_planes_end_to_end(tmp_path):
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import segnet_train_synth as syn
     z = syn.write(str(tmp_path / 'data'), 8, 3, 64, 128)
-    common = ['--train_img_zip', z[0], '--train_label_zip', z[1], '--val_img_zip', z[2], '--val_label_zip', z[3],
-              '--batchsize', '2', '--input_shape', '64', '128', '--eval_shape', '64', '128',
-              '--train_limit', str(E2E_ITERS), 'iteration', '--val_interval', '20', 'iteration',
-              '--log_interval', '10', 'iteration', '--decay_iteration', '30']
+    common = syn.train_args(z, E2E_ITERS, 20, 10, extra=['--decay_iteration', '30'])
     d1, d2 = str(tmp_path / 'run'), str(tmp_path / 'run_val_split')
-    _run([os.path.join(ROOT, 'train_segnet.py')] + common + ['--result_dir', d1], ROOT)
-    _run([os.path.join(ROOT, 'train_segnet.py')] + common + ['--result_dir', d2, '--val_split_planes'], ROOT)
+    syn.run_python([os.path.join(ROOT, 'train_segnet.py')] + common + ['--result_dir', d1], ROOT)
+    syn.run_python([os.path.join(ROOT, 'train_segnet.py')] + common + ['--result_dir', d2, '--val_split_planes'], ROOT)
     # validation on split planes: logged, recorded in args.txt only when given, and without influence on the training
     log1, log2 = (json.load(open(os.path.join(d, 'log'))) for d in (d1, d2))
     print('val/main/iou/road: float32 validation %.4f, split-plane validation %.4f'
@@ -615,8 +383,8 @@ def test_train_then_label_split_planes_end_to_end(tmp_path):
                  '--img_zip_fn', z[2], '--label_zip_fn', z[3], '--start_index', '0', '--end_index', '3',
                  '--eval_shape', '64', '128', '--no_figure']
     out_s, out_f = str(tmp_path / 'labels_split'), str(tmp_path / 'labels')
-    _run(label_cmd + ['--out_dir', out_s, '--split_planes'], ROOT)
-    _run(label_cmd + ['--out_dir', out_f], ROOT)
+    syn.run_python(label_cmd + ['--out_dir', out_s, '--split_planes'], ROOT)
+    syn.run_python(label_cmd + ['--out_dir', out_f], ROOT)
     lines = [json.loads(l) for l in open(os.path.join(out_s, 'result.json')) if l.strip()]
     assert len(lines) == 3
     TP = FP = FN = 0

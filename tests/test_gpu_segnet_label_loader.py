@@ -5,12 +5,10 @@ batches fall back to the host path or a label is refused; the CLI; and what a lo
 runs under a time limit; a failing child ends the test."""
 import ctypes
 import importlib
-import io
 import json
 import os
 import subprocess
 import sys
-import zipfile
 
 import numpy as np
 import pytest
@@ -23,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import segnet_ref as sref  # noqa: E402
 import segnet_train_synth as syn  # noqa: E402
 
 segnet = importlib.import_module('superpixel-align_amd.segnet')
@@ -39,11 +38,6 @@ SHAPES = [((32, 48), (64, 96)), ((40, 56), (97, 131)), ((64, 96), (64, 96)), ((1
 @pytest.fixture(scope='module')
 def eng():
     return importlib.import_module('superpixel-align_amd.engine').default_engine()
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 def _prob(src, B=3, seed=18):
@@ -86,12 +80,12 @@ def test_label_eval_equals_score_confusion_and_pillow(eng, src, dst, want_scores
     assert np.array_equal(mask.cpu().numpy(), mask0.cpu().numpy())
     if want_scores:
         assert sc.dtype == torch.float32 and tuple(sc.shape) == (3, 2) + dst
-        assert np.array_equal(_bits(sc.cpu().numpy()), _bits(sc0.cpu().numpy()))
+        assert np.array_equal(syn.bits(sc.cpu().numpy()), syn.bits(sc0.cpu().numpy()))
         ph = prob.cpu().numpy()
         for bi in range(3):
             want = np.stack([np.asarray(Image.fromarray(c, mode='F').resize(dst[::-1], Image.BILINEAR), np.float32)
                              for c in ph[bi]])
-            assert np.array_equal(_bits(sc[bi].cpu().numpy()), _bits(want))
+            assert np.array_equal(syn.bits(sc[bi].cpu().numpy()), syn.bits(want))
     else:
         assert sc is None
     assert counts.dtype == torch.int64 and tuple(counts.shape) == (3, 4)
@@ -102,7 +96,7 @@ def test_label_eval_equals_score_confusion_and_pillow(eng, src, dst, want_scores
     mask1, sc1, none = eng.segnet_label_eval(prob, dst, None, want_scores=want_scores)
     assert none is None and torch.equal(mask1, mask0) and (sc1 is None) == (not want_scores)
     if want_scores:
-        assert np.array_equal(_bits(sc1.cpu().numpy()), _bits(sc0.cpu().numpy()))
+        assert np.array_equal(syn.bits(sc1.cpu().numpy()), syn.bits(sc0.cpu().numpy()))
 
 
 def test_label_eval_batch_position(eng):
@@ -118,9 +112,9 @@ def test_label_eval_batch_position(eng):
     torch.cuda.synchronize()
     for pos in (0, 2):
         assert torch.equal(a[0][0], b[0][pos]) and torch.equal(a[2][0], b[2][pos])
-        assert np.array_equal(_bits(a[1][0].cpu().numpy()), _bits(b[1][pos].cpu().numpy()))
+        assert np.array_equal(syn.bits(a[1][0].cpu().numpy()), syn.bits(b[1][pos].cpu().numpy()))
     assert torch.equal(b[0], c[0]) and torch.equal(b[2], c[2])
-    assert np.array_equal(_bits(b[1].cpu().numpy()), _bits(c[1].cpu().numpy()))
+    assert np.array_equal(syn.bits(b[1].cpu().numpy()), syn.bits(c[1].cpu().numpy()))
 
 
 def test_label_eval_refusals_launch_nothing(eng):
@@ -157,43 +151,6 @@ H, W = 64, 96
 IN_SHAPE = (32, 48)
 
 
-def _random_params(seed):
-    """Chainer-layout parameters scaled so activations stay O(1)"""
-    rng = np.random.default_rng(seed)
-    p = {}
-    for i, name in enumerate(segnet.LAYERS):
-        cin = 3 if i == 0 else 64
-        p[name + '/W'] = (rng.standard_normal((64, cin, 7, 7)) * np.sqrt(2.0 / (cin * 49))).astype(np.float32)
-        p[name + '_bn/gamma'] = rng.uniform(0.5, 1.5, 64).astype(np.float32)
-        p[name + '_bn/beta'] = rng.uniform(-0.2, 0.2, 64).astype(np.float32)
-        p[name + '_bn/avg_mean'] = rng.uniform(-0.2, 0.2, 64).astype(np.float32)
-        p[name + '_bn/avg_var'] = rng.uniform(0.5, 2.0, 64).astype(np.float32)
-    p['conv_classifier/W'] = (rng.standard_normal((2, 64, 1, 1)) / 4).astype(np.float32)
-    p['conv_classifier/b'] = rng.uniform(-0.1, 0.1, 2).astype(np.float32)
-    return p
-
-
-def _png(a):
-    from PIL import Image
-    b = io.BytesIO()
-    Image.fromarray(a).save(b, format='PNG')
-    return b.getvalue()
-
-
-def _decoded(data):
-    from PIL import Image
-    with Image.open(io.BytesIO(data)) as f:
-        return np.asarray(f)
-
-
-def _rewrite(src, dst, changes):
-    with zipfile.ZipFile(src) as zi, zipfile.ZipFile(dst, 'w') as zo:
-        for k, name in enumerate(zi.namelist()):
-            data = zi.read(name)
-            zo.writestr(name, changes[k](data) if k in changes else data)
-    return dst
-
-
 @pytest.fixture(scope='module')
 def labset(tmp_path_factory):
     d = tmp_path_factory.mktemp('label_loader')
@@ -203,13 +160,13 @@ def labset(tmp_path_factory):
     with open(str(param_dir / 'args.txt'), 'w') as f:
         json.dump({'model': 'basic', 'input_shape': list(IN_SHAPE), 'batchsize': 2}, f)
     with open(str(param_dir / 'snapshot_iter_7'), 'wb') as f:
-        np.savez(f, **{segnet.PREFIX + k: v for k, v in _random_params(24).items()})
+        np.savez(f, **{segnet.PREFIX + k: v for k, v in sref.random_params(24).items()})
     rng = np.random.default_rng(2)
     # the fall-back set: frame 2 stored larger (its label is not), frame 4 as a grey PNG
-    fb_imgs = _rewrite(z[2], str(d / 'fb_imgs.zip'),
-                       {2: lambda b: _png(rng.integers(0, 256, (80, 112, 3), dtype=np.uint8)),
-                        4: lambda b: _png(_decoded(b)[:, :, 1].copy())})
-    bad_labs = _rewrite(z[3], str(d / 'bad_labs.zip'), {3: lambda b: _png(_decoded(b)[:48].copy())})
+    fb_imgs = syn.rewrite(z[2], str(d / 'fb_imgs.zip'),
+                          {2: lambda b: syn.png(rng.integers(0, 256, (80, 112, 3), dtype=np.uint8)),
+                           4: lambda b: syn.png(syn.decoded(b)[:, :, 1].copy())})
+    bad_labs = syn.rewrite(z[3], str(d / 'bad_labs.zip'), {3: lambda b: syn.png(syn.decoded(b)[:48].copy())})
     return dict(dir=d, imgs=z[2], labs=z[3], fb_imgs=fb_imgs, bad_labs=bad_labs, param_dir=str(param_dir))
 
 
@@ -234,12 +191,7 @@ def _same_arrays(a, b):
     assert [os.path.basename(k) for k in a] == [os.path.basename(k) for k in b]
     for (ka, va), (kb, vb) in zip(a.items(), b.items()):
         assert va.dtype == vb.dtype and va.shape == vb.shape and va.flags.owndata and vb.flags.owndata, ka
-        assert np.array_equal(_bits(va), _bits(vb)), ka
-
-
-def _shm_names():
-    """the shared-memory blocks Python's SharedMemory creates (the loaders' slabs are such)"""
-    return set(f for f in os.listdir('/dev/shm') if f.startswith('psm_'))
+        assert np.array_equal(syn.bits(va), syn.bits(vb)), ka
 
 
 def _workers_gone(stats, shm_before):
@@ -251,13 +203,13 @@ def _workers_gone(stats, shm_before):
         except OSError:
             pass
     assert [p for p in multiprocessing.active_children() if p.pid in stats['worker_pids']] == []
-    assert _shm_names() == shm_before
+    assert syn.shm_names('psm_') == shm_before
 
 
 @pytest.mark.parametrize('split', [False, True])
 def test_save_labels_with_the_loader_equals_the_plain_loop(labset, tmp_path, split):
     kw = {'split_planes': True} if split else {}
-    shm_before = _shm_names()
+    shm_before = syn.shm_names('psm_')
     plain, loaded = str(tmp_path / 'plain'), str(tmp_path / 'loaded')
     stats = {}
     _save(labset, plain, 0, **kw)
@@ -296,7 +248,7 @@ def test_save_labels_bf16_with_the_loader_completes(labset, tmp_path):
 
 
 def test_fallback_batches_and_a_refused_label(labset, tmp_path):
-    shm_before = _shm_names()
+    shm_before = syn.shm_names('psm_')
     plain, loaded = str(tmp_path / 'plain'), str(tmp_path / 'loaded')
     stats = {}
     _save(labset, plain, 0, imgs=labset['fb_imgs'])

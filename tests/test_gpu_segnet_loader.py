@@ -4,11 +4,8 @@ with the loader against the same run without it (losses, every snapshot entry, -
 ranks on one GPU with and without it; and what a loader run leaves behind, also one that fails in a step.  Every
 child runs under a time limit; a failing child ends the test."""
 import importlib
-import io
 import json
 import os
-import socket
-import subprocess
 import sys
 import uuid
 import zipfile
@@ -43,10 +40,6 @@ def eng():
     return importlib.import_module('superpixel-align_amd.engine').default_engine()
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _draws(B, rng, augment):
     if not augment:
         return None, None
@@ -78,7 +71,7 @@ def test_train_input_equals_the_dataset_functions(eng, monkeypatch, backend, src
             img = st.resize_bicubic_float(img, dst)
         if augment:
             img, _ = DS.augmented(img, np.zeros(dst, np.int32), shifts[j], bool(flips[j]))
-        n = int((_bits(got[j]) != _bits(img)).sum())
+        n = int((syn.bits(got[j]) != syn.bits(img)).sum())
         print('%s %s -> %s augment %d image %d: %d differing values' % (backend, src, dst, augment, j, n))
         assert n == 0
 
@@ -107,51 +100,24 @@ def test_train_label_equals_the_dataset_functions(eng, monkeypatch, backend, src
         if augment and flips[j]:
             m, s = m[..., ::-1], s[..., ::-1]
         assert np.array_equal(got_m[j], m)
-        assert np.array_equal(_bits(got_s[j]), _bits(s))
+        assert np.array_equal(syn.bits(got_s[j]), syn.bits(s))
 
 
 # ------------------------------------------------------------------------------- train_segnet.py
-def _port():
-    with socket.socket() as s:
-        s.bind(('127.0.0.1', 0))
-        return s.getsockname()[1]
-
-
-def _env(**kw):
-    env = {k: v for k, v in os.environ.items()
-           if k not in ('SPA_DIST_FORCE', 'SPA_DIST_BACKEND', 'SPA_BENCH_SAME_DEVICE', 'RANK', 'WORLD_SIZE',
-                        'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
-    env.update(kw)
-    return env
-
-
 def _run(cmd, env, ok=True):
-    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=TIMEOUT)
-    if ok:
-        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return r
+    return syn.run(cmd, env, ROOT, TIMEOUT, ok)
 
 
 def _common(z, iters, every, extra=()):
-    return ['--train_img_zip', z[0], '--train_label_zip', z[1], '--val_img_zip', z[2], '--val_label_zip', z[3],
-            '--batchsize', '2', '--input_shape', '32', '64', '--eval_shape', '48', '96', '--random',
-            '--optimizer', 'MomentumSGD', '--train_limit', str(iters), 'iteration',
-            '--val_interval', str(every), 'iteration', '--log_interval', str(every), 'iteration'] + list(extra)
+    return syn.train_args(z, iters, every, every, (32, 64), (48, 96),
+                          ['--random', '--optimizer', 'MomentumSGD'] + list(extra))
 
 
 def _same_snapshot(fa, fb):
-    with np.load(fa) as a, np.load(fb) as b:
-        assert set(a.files) == set(b.files)
-        for k in a.files:
-            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
-        assert 'extensions/np_random/keys' in a.files and 'updater/iterator:main/order' in a.files
-        assert any(k.startswith('updater/optimizer:main/predictor/') for k in a.files)
-        return len(a.files)
-
-
-def _losses(d):
-    return [(e['iteration'], e['epoch'], e['main/loss'], e['val/main/iou/road']) for e in
-            json.load(open(os.path.join(d, 'log')))]
+    ks = syn.same_snapshot(fa, fb, bitwise=True)
+    assert 'extensions/np_random/keys' in ks and 'updater/iterator:main/order' in ks
+    assert any(k.startswith('updater/optimizer:main/predictor/') for k in ks)
+    return len(ks)
 
 
 def test_loader_run_equals_plain_run_and_resumes_both_ways(tmp_path):
@@ -159,38 +125,38 @@ def test_loader_run_equals_plain_run_and_resumes_both_ways(tmp_path):
     inside batches), snapshots at 6 and 12"""
     z = syn.write(str(tmp_path / 'data'), 5, 2, 48, 96)
     d = {k: str(tmp_path / k) for k in ('plain', 'loader', 'from_loader', 'from_plain')}
-    _run([sys.executable, SCRIPT] + _common(z, 12, 6) + ['--result_dir', d['plain']], _env())
+    _run([sys.executable, SCRIPT] + _common(z, 12, 6) + ['--result_dir', d['plain']], syn.env())
     r = _run([sys.executable, SCRIPT, '--loader_procs', '2'] + _common(z, 12, 6) + ['--result_dir', d['loader']],
-             _env())
+             syn.env())
     assert 'prepared on the host' not in r.stdout
     assert json.load(open(os.path.join(d['loader'], 'args.txt')))['loader_procs'] == 2
     assert 'loader_procs' not in json.load(open(os.path.join(d['plain'], 'args.txt')))
-    assert _losses(d['plain']) == _losses(d['loader']) and len(_losses(d['plain'])) == 2
+    assert syn.losses(d['plain']) == syn.losses(d['loader']) and len(syn.losses(d['plain'])) == 2
     for it in (6, 12):
         n = _same_snapshot(os.path.join(d['plain'], 'snapshot_iter_%d' % it),
                            os.path.join(d['loader'], 'snapshot_iter_%d' % it))
         assert n > 60
     # resume: the loader run's snapshot without the flag, the plain run's snapshot with it
     _run([sys.executable, SCRIPT] + _common(z, 12, 6) +
-         ['--result_dir', d['from_loader'], '--resume', os.path.join(d['loader'], 'snapshot_iter_6')], _env())
+         ['--result_dir', d['from_loader'], '--resume', os.path.join(d['loader'], 'snapshot_iter_6')], syn.env())
     _run([sys.executable, SCRIPT, '--loader_procs', '2'] + _common(z, 12, 6) +
-         ['--result_dir', d['from_plain'], '--resume', os.path.join(d['plain'], 'snapshot_iter_6')], _env())
+         ['--result_dir', d['from_plain'], '--resume', os.path.join(d['plain'], 'snapshot_iter_6')], syn.env())
     for k in ('from_loader', 'from_plain'):
         _same_snapshot(os.path.join(d['plain'], 'snapshot_iter_12'), os.path.join(d[k], 'snapshot_iter_12'))
-        assert _losses(d[k])[-1][:3] == _losses(d['plain'])[-1][:3]
+        assert syn.losses(d[k])[-1][:3] == syn.losses(d['plain'])[-1][:3]
 
 
 def test_two_gloo_ranks_with_the_loader_equal_the_launch_without(tmp_path):
     z = syn.write(str(tmp_path / 'data'), 9, 2, 48, 96)
-    env = _env(SPA_DIST_BACKEND='gloo', SPA_BENCH_SAME_DEVICE='1')
+    env = syn.env(SPA_DIST_BACKEND='gloo', SPA_BENCH_SAME_DEVICE='1')
 
     def torchrun(argv):
         return [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
-                '--master-addr', '127.0.0.1', '--master-port', str(_port()), SCRIPT] + argv
+                '--master-addr', '127.0.0.1', '--master-port', str(syn.free_port()), SCRIPT] + argv
     da, db = str(tmp_path / 'plain'), str(tmp_path / 'loader')
     _run(torchrun(['--data_parallel'] + _common(z, 8, 4) + ['--result_dir', da]), env)
     _run(torchrun(['--data_parallel', '--loader_procs', '2'] + _common(z, 8, 4) + ['--result_dir', db]), env)
-    assert _losses(da) == _losses(db)
+    assert syn.losses(da) == syn.losses(db)
     for it in (4, 8):
         _same_snapshot(os.path.join(da, 'snapshot_iter_%d' % it), os.path.join(db, 'snapshot_iter_%d' % it))
     assert st.snapshot_world_size(os.path.join(db, 'snapshot_iter_8')) == 2
@@ -214,12 +180,6 @@ def _marked_processes(mark):
     return out
 
 
-def _npy(a):
-    buf = io.BytesIO()
-    np.save(buf, a)
-    return buf.getvalue()
-
-
 def test_nothing_is_left_after_a_run_or_a_failing_step(tmp_path):
     z = syn.write(str(tmp_path / 'data'), 5, 2, 48, 96)
     # scores with three channels: the soft-label loss of the first step refuses them against the two-channel output
@@ -227,17 +187,17 @@ def test_nothing_is_left_after_a_run_or_a_failing_step(tmp_path):
     rng = np.random.default_rng(1)
     with zipfile.ZipFile(z[1]) as zl, zipfile.ZipFile(bad, 'w', zipfile.ZIP_STORED) as zo:
         for name in zl.namelist():
-            zo.writestr(name[:-len('.npy')] + '_scores.npy', _npy(rng.random((3, 48, 96)).astype(np.float32)))
+            zo.writestr(name[:-len('.npy')] + '_scores.npy', syn.npy(rng.random((3, 48, 96)).astype(np.float32)))
     before = set(os.listdir('/dev/shm'))
     mark = 'SPA_TEST_MARK_%s' % uuid.uuid4().hex
     r = _run([sys.executable, SCRIPT, '--loader_procs', '2'] + _common(z, 4, 2) +
-             ['--result_dir', str(tmp_path / 'good')], _env(**{mark: '1'}))
+             ['--result_dir', str(tmp_path / 'good')], syn.env(**{mark: '1'}))
     assert os.path.exists(str(tmp_path / 'good' / 'snapshot_iter_4'))
     assert _marked_processes(mark) == [] and set(os.listdir('/dev/shm')) == before
     assert 'leaked' not in r.stderr
     zb = [z[0], bad, z[2], z[3]]
     r = _run([sys.executable, SCRIPT, '--loader_procs', '2'] + _common(zb, 4, 2, ['--use_soft_label']) +
-             ['--result_dir', str(tmp_path / 'bad')], _env(**{mark: '1'}), ok=False)
+             ['--result_dir', str(tmp_path / 'bad')], syn.env(**{mark: '1'}), ok=False)
     assert r.returncode != 0 and 'Traceback' in r.stderr
     assert not os.path.exists(str(tmp_path / 'bad' / 'snapshot_iter_2'))
     assert _marked_processes(mark) == [] and set(os.listdir('/dev/shm')) == before

@@ -2,12 +2,12 @@
 dtype='bf16'), train_segnet.py --dtype bf16): the eight pass forms against float64 torch convolutions and their
 autograd on the same bf16-rounded operands, the BatchNorm partial sums, NaN-poisoned outputs with a guard past the end,
 bit-identical repeats, refusals that write nothing, one whole bf16 step against the float64 restatement with operand
-rounding, and train_segnet.py --dtype bf16 -> --resume -> labels_from_segnet.py end to end on synthetic zips."""
-import ctypes
+rounding, and train_segnet.py --dtype bf16 -> --resume -> labels_from_segnet.py end to end on synthetic zips.
+The pass checks are the shared bodies of tests/segnet_ref.py, called with this file's family, operand rounding and
+bounds."""
 import importlib
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -16,10 +16,11 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip('torch')
-F = torch.nn.functional
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import segnet_ref as sref  # noqa: E402
+import segnet_train_synth as syn  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-segnet = importlib.import_module('superpixel-align_amd.segnet')
 st = importlib.import_module('superpixel-align_amd.segnet_train')
 
 SHAPES = [(1, 16, 16), (2, 48, 80), (3, 64, 128), (2, 6, 10)]
@@ -31,6 +32,11 @@ SHAPES = [(1, 16, 16), (2, 48, 80), (3, 64, 128), (2, 6, 10)]
 FWD_TOL = 1e-5
 WGRAD_TOL = 1e-5
 WGRAD_BIG_TOL = 2e-5
+BN_TOL = 1e-6             # the BatchNorm partial sums against float64 sums of the kernel's own y
+# bf16 entry points; every operand enters the reference rounded to bf16; conv1's input is the float32 kernels' own
+# operand (checked against the float64 restatement), rounded
+MODE = dict(family='_bf16', operand=sref.r16)
+CONV1 = dict(device_conv1=True, check_conv1=True)
 
 
 @pytest.fixture(scope='module')
@@ -41,212 +47,29 @@ def eng():
     e.close()
 
 
-def poisoned(shape, dtype=torch.float32, guard=1024):
-    """(out view, whole buffer): NaN everywhere, a NaN guard of `guard` elements past the end of the view"""
-    n = int(np.prod(shape))
-    buf = torch.full((n + guard,), float('nan'), dtype=dtype, device='cuda')
-    return buf[:n].view(shape), buf
-
-
-def check_guard(buf, n):
-    assert torch.isnan(buf[n:]).all().item(), 'a kernel wrote past the end of its output'
-
-
-def rel_err(got, ref):
-    got = got.detach().double().cpu()
-    ref = ref.detach().double().cpu()
-    return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-300))
-
-
-def r16(t):
-    """the bf16 operand of a float32 value, as float64"""
-    return st.bf16_round(t.float()).double()
-
-
-def inputs(B, H, W, seed):
-    g = torch.Generator().manual_seed(seed)
-    img = torch.rand((B, 3, H, W), generator=g) * 255.0
-    x = torch.randn((B, H, W, 64), generator=g)
-    h = torch.randn((B, H // 2, W // 2, 64), generator=g)
-    idx = torch.randint(0, 4, (B, H // 2, W // 2, 64), generator=g, dtype=torch.uint8)
-    dy = torch.randn((B, H, W, 64), generator=g)
-    w1 = torch.randn((64, 3, 7, 7), generator=g) * (2.0 / 147) ** 0.5
-    w64 = torch.randn((64, 64, 7, 7), generator=g) * (2.0 / 3136) ** 0.5
-    return img, x, h, idx, dy, w1, w64
-
-
-def nchw(a):
-    return a.permute(0, 3, 1, 2)
-
-
-def conv1_operand(eng, img):
-    """conv1's float32 input exactly as the kernels load it (standardised, LRN in float32): the float32 forward pass
-    with a centre-tap identity weight returns it (one exact product per output), (B,H,W,3) float32"""
-    wid = torch.zeros((64, 3, 7, 7))
-    for c in range(3):
-        wid[c, c, 3, 3] = 1.0
-    wt = torch.from_numpy(segnet.pack_weight(wid.numpy())).cuda()
-    y, _ = eng.segnet_train_forward(img.cuda().contiguous(), wt, None, segnet.MEAN, segnet.STD, stats=False)
-    x1 = y[..., :3].cpu()
-    assert (x1.double() - st.conv1_input(img.double()).permute(0, 2, 3, 1)).abs().max() < 1e-5
-    return x1
-
-
-def ref_forms(eng, img, x, h, idx):
-    """float64 (B,C,H,W) bf16 operands of the three input forms: conv1's image, the map, the unpooled map"""
-    x1 = nchw(r16(conv1_operand(eng, img))) if img.shape[2] % 16 == 0 else None
-    return x1, nchw(r16(x)), st.unpool_ref(nchw(r16(h)), nchw(idx.long()))
-
-
 @pytest.mark.parametrize('shape', SHAPES)
 def test_forward_forms_and_bn_sums(eng, shape):
-    B, H, W = shape
-    img, x, h, idx, dy, w1, w64 = inputs(B, H, W, 1)
-    x1, xe, xd = ref_forms(eng, img, x, h, idx)
-    cases = [('conv1', img, None, w1, x1), ('enc', x, None, w64, xe), ('dec', h, idx, w64, xd)]
-    worst = 0.0
-    for name, xin, ii, w, xref in cases[1:] if H % 16 else cases:
-        wt = torch.from_numpy(segnet.pack_weight(w.numpy())).cuda()
-        out, buf = poisoned((B, H, W, 64))
-        y, stats = eng.segnet_train_forward_bf16(xin.cuda().contiguous(), wt, ii.cuda() if ii is not None else None,
-                                                 segnet.MEAN, segnet.STD, out=out)
-        torch.cuda.synchronize()
-        check_guard(buf, B * H * W * 64)
-        assert not torch.isnan(y).any().item(), '%s: an output was not stored' % name
-        ref = F.conv2d(xref, r16(w), padding=3)                       # (B,64,H,W)
-        e = rel_err(nchw(y), ref)
-        worst = max(worst, e)
-        assert e < FWD_TOL, '%s %s: forward error %.3g' % (name, shape, e)
-        # the BN partial sums are the kernel's own y summed; compare with float64 sums of that y
-        y64 = y.double()
-        s_ref = torch.stack([y64.sum((0, 1, 2)), (y64 * y64).sum((0, 1, 2))])
-        scale = torch.stack([y64.abs().sum((0, 1, 2)), (y64 * y64).sum((0, 1, 2))])
-        es = float(((stats - s_ref).abs() / scale).max())
-        assert es < 1e-6, '%s %s: BN sum error %.3g' % (name, shape, es)
-        # repeat: the same bits
-        y2, stats2 = eng.segnet_train_forward_bf16(xin.cuda().contiguous(), wt,
-                                                   ii.cuda() if ii is not None else None, segnet.MEAN, segnet.STD)
-        assert torch.equal(y2, y) and torch.equal(stats2, stats), '%s: repeat differs' % name
+    worst = sref.check_forward(eng, shape, 1, fwd_tol=FWD_TOL, bn_tol=BN_TOL, **MODE, **CONV1)
     print('bf16 forward %s: worst %.3g' % (shape, worst))
 
 
 @pytest.mark.parametrize('shape', SHAPES)
 def test_dgrad_forms(eng, shape):
-    B, H, W = shape
-    img, x, h, idx, dy, w1, w64 = inputs(B, H, W, 2)
-    wt = torch.from_numpy(segnet.pack_weight(w64.numpy())).cuda()
-    dyd = dy.cuda().contiguous()
-    # encoder: full-resolution input gradient
-    xe = nchw(r16(x)).requires_grad_(True)
-    F.conv2d(xe, r16(w64), padding=3).backward(nchw(r16(dy)))
-    out, buf = poisoned((B, H, W, 64))
-    dx = eng.segnet_train_dgrad_bf16(dyd, wt, out=out)
-    torch.cuda.synchronize()
-    check_guard(buf, B * H * W * 64)
-    assert not torch.isnan(dx).any().item()
-    e1 = rel_err(nchw(dx), xe.grad)
-    assert e1 < FWD_TOL, 'enc dgrad %s: %.3g' % (shape, e1)
-    assert torch.equal(eng.segnet_train_dgrad_bf16(dyd, wt), dx)
-    # decoder: the gradient at the pooled input, through the index map
-    hd = nchw(r16(h)).requires_grad_(True)
-    F.conv2d(st.unpool_ref(hd, nchw(idx.long())), r16(w64), padding=3).backward(nchw(r16(dy)))
-    out, buf = poisoned((B, H // 2, W // 2, 64))
-    dh = eng.segnet_train_dgrad_bf16(dyd, wt, idx.cuda(), out=out)
-    torch.cuda.synchronize()
-    check_guard(buf, B * H * W * 16)
-    assert not torch.isnan(dh).any().item()
-    e2 = rel_err(nchw(dh), hd.grad)
-    assert e2 < FWD_TOL, 'dec dgrad %s: %.3g' % (shape, e2)
-    assert torch.equal(eng.segnet_train_dgrad_bf16(dyd, wt, idx.cuda()), dh)
-    print('bf16 dgrad %s: worst %.3g' % (shape, max(e1, e2)))
-
-
-def wgrad_ref(dy, xin):
-    """float64 on the device: dW[t][n][c] = sum_p dy[p][n] * xin[p + off(t)][c], dy (B,H,W,64), xin (B,H,W,C)"""
-    B, H, W, C = xin.shape
-    xp = F.pad(xin, (0, 0, 3, 3, 3, 3))
-    g = dy.reshape(-1, 64)
-    out = torch.empty((49, 64, C), dtype=torch.float64, device=dy.device)
-    for ky in range(7):
-        for kx in range(7):
-            out[ky * 7 + kx] = g.t() @ xp[:, ky:ky + H, kx:kx + W, :].reshape(-1, C)
-    return out
+    print('bf16 dgrad %s: worst %.3g' % (shape, sref.check_dgrad(eng, shape, 2, fwd_tol=FWD_TOL, **MODE)))
 
 
 @pytest.mark.parametrize('shape', SHAPES)
 def test_wgrad_forms(eng, shape):
-    B, H, W = shape
-    img, x, h, idx, dy, w1, w64 = inputs(B, H, W, 3)
-    x1, xe, xd = ref_forms(eng, img, x, h, idx)
-    dyd = dy.cuda().contiguous()
-    dyr = r16(dy).cuda()
-    cases = [('conv1', img, None, x1, 4), ('enc', x, None, xe, 64), ('dec', h, idx, xd, 64)]
-    worst = 0.0
-    for name, xin, ii, xref, cp in cases[1:] if H % 16 else cases:
-        out, buf = poisoned((49, 64, cp))
-        dw = eng.segnet_train_wgrad_bf16(dyd, xin.cuda().contiguous(), ii.cuda() if ii is not None else None,
-                                         segnet.MEAN, segnet.STD, out=out)
-        torch.cuda.synchronize()
-        check_guard(buf, 49 * 64 * cp)
-        assert not torch.isnan(dw).any().item(), '%s: an output was not stored' % name
-        xr = F.pad(xref, (0, 0, 0, 0, 0, 1)) if cp == 4 else xref      # conv1: channel 3 is zero
-        ref = wgrad_ref(dyr, xr.permute(0, 2, 3, 1).contiguous().cuda())
-        e = rel_err(dw, ref)
-        worst = max(worst, e)
-        assert e < WGRAD_TOL, '%s wgrad %s: %.3g' % (name, shape, e)
-        if cp == 4:
-            assert torch.equal(dw[:, :, 3], torch.zeros_like(dw[:, :, 3]))
-        dw2 = eng.segnet_train_wgrad_bf16(dyd, xin.cuda().contiguous(), ii.cuda() if ii is not None else None,
-                                          segnet.MEAN, segnet.STD)
-        assert torch.equal(dw2, dw), '%s wgrad: repeat differs' % name
+    worst = sref.check_wgrad(eng, shape, 3, wgrad_tol=WGRAD_TOL, **MODE, **CONV1)
     print('bf16 wgrad %s: worst %.3g' % (shape, worst))
 
 
 def test_wgrad_decode1_full_size(eng):
-    """decode1's weight gradient at B = 4, 512 x 1024: K = 2.1e6 products per output, split over the chunks"""
-    B, H, W = 4, 512, 1024
-    g = torch.Generator(device='cuda').manual_seed(4)
-    h = torch.randn((B, H // 2, W // 2, 64), generator=g, device='cuda')
-    idx = torch.randint(0, 4, (B, H // 2, W // 2, 64), generator=g, device='cuda', dtype=torch.uint8)
-    dy = torch.randn((B, H, W, 64), generator=g, device='cuda')
-    dw = eng.segnet_train_wgrad_bf16(dy, h, idx)
-    xd = st.unpool_ref(nchw(r16(h)), nchw(idx.long())).permute(0, 2, 3, 1)
-    ref = wgrad_ref(r16(dy), xd.contiguous())
-    del xd
-    e = rel_err(dw, ref)
-    print('bf16 decode1 wgrad (4,512,1024): %.3g' % e)
-    assert e < WGRAD_BIG_TOL, 'decode1 wgrad at (4,512,1024): %.3g' % e
-    assert torch.equal(eng.segnet_train_wgrad_bf16(dy, h, idx), dw)
+    sref.check_wgrad_decode1_full_size(eng, big_tol=WGRAD_BIG_TOL, label='bf16', **MODE)
 
 
 def test_refusals_write_nothing(eng):
-    lib, ctx = eng._lib, eng._ctx
-    s = eng._s()
-    x = torch.randn((1, 25, 32, 64), device='cuda')                  # H odd
-    wt = torch.randn((49, 64, 64), device='cuda')
-    out, buf = poisoned((1, 25, 32, 64))
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-    rc = lib.spa_segnet_train_forward_bf16(ctx, p(x), None, 0, 1, 25, 32, 64, p(wt), None, None, p(out), None, s)
-    assert rc != 0
-    rc = lib.spa_segnet_train_dgrad_bf16(ctx, p(x), p(wt), None, 1, 25, 32, p(out), s)
-    assert rc != 0
-    dw, dbuf = poisoned((49, 64, 64))
-    rc = lib.spa_segnet_train_wgrad_bf16(ctx, p(x), p(x), None, 0, 1, 25, 32, 64, None, None, p(dw), s)
-    assert rc != 0
-    x16 = torch.randn((1, 16, 32, 64), device='cuda')
-    rc = lib.spa_segnet_train_wgrad_bf16(ctx, p(x16), p(x16), None, 1, 1, 16, 32, 64, None, None, p(dw), s)   # planar
-    assert rc != 0
-    img = torch.randn((1, 3, 16, 24), device='cuda')                 # conv1: W not a multiple of 16
-    m3 = (ctypes.c_float * 3)(1, 1, 1)
-    rc = lib.spa_segnet_train_forward_bf16(ctx, p(img), None, 1, 1, 16, 24, 3, p(wt), m3, m3, p(out), None, s)
-    assert rc != 0
-    rc = lib.spa_segnet_train_forward_bf16(ctx, p(img), None, 0, 1, 16, 32, 3, p(wt), None, None, p(out), None, s)
-    assert rc != 0                                                   # conv1 without mean / std, and channels-last
-    wt_off = torch.randn((49 * 64 * 64 + 4,), device='cuda')[1:]     # weights not 16-byte aligned
-    rc = lib.spa_segnet_train_dgrad_bf16(ctx, p(x16), p(wt_off), None, 1, 16, 32, p(out), s)
-    assert rc != 0
-    torch.cuda.synchronize()
-    assert torch.isnan(buf).all().item() and torch.isnan(dbuf).all().item()
+    sref.check_train_refusals(eng, '_bf16', unaligned_weights=True)
 
 
 # ------------------------------------------------------------------------------- one whole training step
@@ -265,60 +88,24 @@ LOSS_VS_FP32 = 1e-2      # the bf16 step's loss against the float32 step's, rela
 
 
 def test_full_bf16_training_step_against_float64(eng):
-    B, H, W = 2, 64, 128
-    p = st.init_params(5)
-    g = torch.Generator().manual_seed(6)
-    img = torch.rand((B, 3, H, W), generator=g) * 255
-    t = torch.randint(-1, 2, (B, H, W), generator=g)
-    tr = st.SegNetTrainer(p, st.MomentumSGD(0.01, weight_decay=0.0005), st.softmax_cross_entropy, engine=eng,
-                          dtype='bf16')
-    before = {k: v.clone() for k, v in tr.P.items()}
-    trace = []
-    loss = tr.step(img.cuda(), t.cuda(), trace)
-    P64 = {k: torch.tensor(p[k], dtype=torch.float64, requires_grad=True) for k in st.PARAM_KEYS}
-    S64 = {k: torch.tensor(p[k], dtype=torch.float64) for k in st.STAT_KEYS}
-    maps = [m.cpu() for m in trace]
-    l64, _ = st.reference_loss(P64, S64, img.double(), t, st.softmax_cross_entropy, idx_maps=maps,
-                               bf16_operands=True)
-    grads = dict(zip(P64.keys(), torch.autograd.grad(l64, list(P64.values()))))
-    with torch.no_grad():
-        Q = {k: v.detach().clone() for k, v in P64.items()}
-        st.MomentumSGD(0.01, weight_decay=0.0005).update(Q, grads)
-    worst = {}
-    for k in st.PARAM_KEYS:
-        d_gpu = (tr.P[k].double().cpu() - before[k].double().cpu())
-        d_ref = Q[k] - P64[k].detach()
-        worst[k] = float((d_gpu - d_ref).abs().max() / d_ref.abs().max())
+    r = sref.step_against_float64(eng, dict(dtype='bf16'), bf16_operands=True)
+    loss, l64, worst, es = r['loss'], r['l64'], r['updates'], r['stats']
     kmax = max(worst, key=worst.get)
-    print('bf16 step: loss %.6g (float64 %.6g), worst update error %.3g (%s)' % (loss, l64.item(), worst[kmax], kmax))
+    print('bf16 step: loss %.6g (float64 %.6g), worst update error %.3g (%s)' % (loss, l64, worst[kmax], kmax))
     assert worst[kmax] < STEP_TOL, '%s: update error %.3g' % (kmax, worst[kmax])
-    es = {k: float((tr.S[k].double().cpu() - S64[k]).abs().max() / S64[k].abs().max()) for k in st.STAT_KEYS}
     kmax = max(es, key=es.get)
     print('bf16 step: worst running statistic error %.3g (%s)' % (es[kmax], kmax))
     assert es[kmax] < STAT_TOL, '%s: running statistic error %.3g' % (kmax, es[kmax])
     # against the float32 step on the same parameters and batch
-    tr32 = st.SegNetTrainer(p, st.MomentumSGD(0.01, weight_decay=0.0005), st.softmax_cross_entropy, engine=eng)
-    loss32 = tr32.step(img.cuda(), t.cuda())
+    tr32 = st.SegNetTrainer(r['p'], st.MomentumSGD(0.01, weight_decay=0.0005), st.softmax_cross_entropy, engine=eng)
+    loss32 = tr32.step(r['img'].cuda(), r['t'].cuda())
     print('bf16 step: loss %.6g, float32 step %.6g' % (loss, loss32))
     assert abs(loss - loss32) < LOSS_VS_FP32 * abs(loss32)
-    assert abs(loss - l64.item()) < LOSS_VS_FP32 * abs(l64.item())
+    assert abs(loss - l64) < LOSS_VS_FP32 * abs(l64)
 
 
 def test_bf16_step_repeats_bit_for_bit(eng):
-    B, H, W = 2, 32, 64
-    p = st.init_params(7)
-    g = torch.Generator().manual_seed(8)
-    img = (torch.rand((B, 3, H, W), generator=g) * 255).cuda()
-    t = torch.randint(-1, 2, (B, H, W), generator=g).cuda()
-    runs = []
-    for _ in range(2):
-        tr = st.SegNetTrainer(p, st.MomentumSGD(0.01, weight_decay=0.0005), st.softmax_cross_entropy, engine=eng,
-                              dtype='bf16')
-        losses = [tr.step(img, t) for _ in range(2)]
-        runs.append((losses, {k: v.clone() for k, v in tr.P.items()}))
-    assert runs[0][0] == runs[1][0]
-    for k in st.PARAM_KEYS:
-        assert torch.equal(runs[0][1][k], runs[1][1][k]), k
+    sref.check_step_repeats(eng, dtype='bf16')
 
 
 # ------------------------------------------------------------------------------- end to end
@@ -328,23 +115,12 @@ E2E_LOSS_FRACTION = 0.35
 E2E_MIN_IOU = 0.6
 
 
-def _run(args, cwd):
-    r = subprocess.run([sys.executable] + args, cwd=cwd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return r
-
-
 def test_train_bf16_then_label_end_to_end(tmp_path):
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import segnet_train_synth as syn
     z = syn.write(str(tmp_path / 'data'), 8, 3, 64, 128)
-    common = ['--train_img_zip', z[0], '--train_label_zip', z[1], '--val_img_zip', z[2], '--val_label_zip', z[3],
-              '--batchsize', '2', '--input_shape', '64', '128', '--eval_shape', '64', '128',
-              '--train_limit', str(E2E_ITERS), 'iteration', '--val_interval', '20', 'iteration',
-              '--log_interval', '10', 'iteration', '--decay_iteration', '30']
+    common = syn.train_args(z, E2E_ITERS, 20, 10, extra=['--decay_iteration', '30'])
     d1, d2, d3 = str(tmp_path / 'run'), str(tmp_path / 'resumed'), str(tmp_path / 'resumed_fp32')
     script = os.path.join(ROOT, 'train_segnet.py')
-    _run([script, '--dtype', 'bf16'] + common + ['--result_dir', d1], ROOT)
+    syn.run_python([script, '--dtype', 'bf16'] + common + ['--result_dir', d1], ROOT)
     log = json.load(open(os.path.join(d1, 'log')))
     print('bf16 end to end: loss %s, road IoU %.4f' % ([round(e['main/loss'], 4) for e in log],
                                                       log[-1]['val/main/iou/road']))
@@ -357,20 +133,20 @@ def test_train_bf16_then_label_end_to_end(tmp_path):
     snap20 = os.path.join(d1, 'snapshot_iter_20')
     assert st.snapshot_dtype(snap20) == 'bf16'
     # --resume from the middle in the same dtype reaches the same snapshot, bit for bit
-    _run([script, '--dtype', 'bf16'] + common + ['--result_dir', d2, '--resume', snap20], ROOT)
+    syn.run_python([script, '--dtype', 'bf16'] + common + ['--result_dir', d2, '--resume', snap20], ROOT)
     with np.load(os.path.join(d1, 'snapshot_iter_40')) as a, np.load(os.path.join(d2, 'snapshot_iter_40')) as b:
         assert set(a.files) == set(b.files)
         for k in a.files:
             assert np.array_equal(a[k], b[k]), k
     # a bf16 snapshot resumes in float32 too (float32 master weights and optimizer state)
-    r = _run([script] + common + ['--result_dir', d3, '--resume', snap20], ROOT)
+    r = syn.run_python([script] + common + ['--result_dir', d3, '--resume', snap20], ROOT)
     assert 'resuming a bf16 snapshot in fp32' in r.stdout
     assert st.snapshot_dtype(os.path.join(d3, 'snapshot_iter_40')) == 'fp32'
     log3 = json.load(open(os.path.join(d3, 'log')))
     assert log3[-1]['val/main/iou/road'] > E2E_MIN_IOU, log3[-1]
     # labels_from_segnet.py on the bf16 trainer's snapshot predicts what the trainer's validation predicted
     out = str(tmp_path / 'labels')
-    _run([os.path.join(ROOT, 'labels_from_segnet.py'), '--param_dir', d1, '--iteration', str(E2E_ITERS),
+    syn.run_python([os.path.join(ROOT, 'labels_from_segnet.py'), '--param_dir', d1, '--iteration', str(E2E_ITERS),
           '--img_zip_fn', z[2], '--label_zip_fn', z[3], '--out_dir', out, '--start_index', '0', '--end_index', '3',
           '--eval_shape', '64', '128', '--no_figure'], ROOT)
     res = [json.loads(l) for l in open(os.path.join(out, 'result.json')) if l.strip()]

@@ -1,7 +1,7 @@
-"""SegNet-Basic host side (no GPU): snapshot loading with the reference's selection quirks, BatchNorm folding, the
-labels_from_segnet.py CLI, the zipped dataset and the host form of the Pillow BILINEAR score resize."""
+"""SegNet-Basic host side (no GPU): snapshot loading with the reference's selection quirks, BatchNorm folding (on the
+float64 restatement of tests/segnet_ref.py, which the GPU tests share), the labels_from_segnet.py CLI, the zipped
+dataset and the host form of the Pillow BILINEAR score resize."""
 import importlib
-import io
 import json
 import os
 import sys
@@ -10,11 +10,13 @@ import zipfile
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import segnet_ref as sref  # noqa: E402
+import segnet_train_synth as syn  # noqa: E402
 segnet = importlib.import_module('superpixel-align_amd.segnet')
 cli = importlib.import_module('superpixel-align_amd.cli')
 
@@ -87,56 +89,12 @@ def test_snapshot_refusals(tmp_path):
 
 
 # ------------------------------------------------------------------------------- BN folding
-def lrn_chainer(x):
-    """Chainer's local_response_normalization(x, 5, 1, 1e-4 / 5, 0.75): alpha NOT divided by n (3 channels: all)."""
-    s = (x * x).sum(1, keepdim=True)
-    return x * (1.0 + 1e-4 / 5 * s) ** -0.75
-
-
-def pool_argmax(h):
-    B, C, H, W = h.shape
-    win = h.reshape(B, C, H // 2, 2, W // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, C, H // 2, W // 2, 4)
-    idx = win.argmax(-1)          # ties -> first (torch CPU argmax returns the first maximal index)
-    return win.gather(-1, idx[..., None])[..., 0], idx
-
-
-def unpool(h, idx):
-    B, C, h2, w2 = h.shape
-    out = torch.zeros(B, C, h2, w2, 4, dtype=h.dtype)
-    out.scatter_(-1, idx[..., None], h[..., None])
-    return out.reshape(B, C, h2, w2, 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, C, 2 * h2, 2 * w2)
-
-
-def forward64(params, x, folded):
-    """float64 restatement of segnet_basic.py __call__ + softmax, BN unfolded (test mode) or folded."""
-    f = segnet.fold_bn(params, np.float64) if folded else None
-    t = lambda a: torch.from_numpy(np.asarray(a, np.float64))
-
-    def layer(name, h):
-        if folded:
-            w, b = f[name]
-            return F.conv2d(h, t(w), t(b), padding=3)
-        y = F.conv2d(h, t(params[name + '/W']), padding=3)
-        g, be, mu, var = (t(params['%s_bn/%s' % (name, k)])[None, :, None, None] for k in segnet.BN_PARAMS)
-        return g * (y - mu) / torch.sqrt(var + segnet.BN_EPS) + be
-
-    h = lrn_chainer(x)
-    idxs = []
-    for name in segnet.ENCODERS:
-        h, i = pool_argmax(torch.relu(layer(name, h)))
-        idxs.append(i)
-    for name, i in zip(segnet.DECODERS, idxs[::-1]):
-        h = layer(name, unpool(h, i))
-    z = F.conv2d(h, t(params['conv_classifier/W']), t(params['conv_classifier/b']))
-    return torch.softmax(z, 1), h
-
-
 def test_bn_folding_float64():
     rng = np.random.default_rng(3)
     p = random_params(rng)
     x = torch.from_numpy(rng.standard_normal((1, 3, 32, 48)))
-    pu, hu = forward64(p, x, folded=False)
-    pf, hf = forward64(p, x, folded=True)
+    pu, hu = sref.forward64(p, x)                                 # BN unfolded (test mode), as the model states it
+    pf, hf = sref.forward64(p, x, layer=sref.folded_conv)
     scale = float(hu.abs().max())
     assert float((hu - hf).abs().max()) <= 1e-12 * scale
     assert float((pu - pf).abs().max()) <= 1e-12
@@ -173,13 +131,6 @@ def test_cli_defaults_match_reference():
 
 
 # ------------------------------------------------------------------------------- dataset
-def png_bytes(a):
-    from PIL import Image
-    b = io.BytesIO()
-    Image.fromarray(a).save(b, format='PNG')
-    return b.getvalue()
-
-
 def make_zips(tmp_path, keys, extra_label_keys=(), H=24, W=40, seed=5):
     rng = np.random.default_rng(seed)
     img_zip, label_zip = str(tmp_path / 'img.zip'), str(tmp_path / 'label.zip')
@@ -188,13 +139,13 @@ def make_zips(tmp_path, keys, extra_label_keys=(), H=24, W=40, seed=5):
         for k in keys:
             city = k.split('_')[0]
             imgs[k] = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
-            zi.writestr('leftImg8bit/val/%s/%s_leftImg8bit.png' % (city, k), png_bytes(imgs[k]))
+            zi.writestr('leftImg8bit/val/%s/%s_leftImg8bit.png' % (city, k), syn.png(imgs[k]))
         zi.writestr('leftImg8bit/val/README.txt', b'not an image')
         for k in list(keys) + list(extra_label_keys):
             city = k.split('_')[0]
             labels[k] = rng.integers(0, 12, (H, W), dtype=np.uint8)
-            zl.writestr('gtFine/val/%s/%s_gtFine_labelIds.png' % (city, k), png_bytes(labels[k]))
-            zl.writestr('gtFine/val/%s/%s_gtFine_color.png' % (city, k), png_bytes(labels[k]))
+            zl.writestr('gtFine/val/%s/%s_gtFine_labelIds.png' % (city, k), syn.png(labels[k]))
+            zl.writestr('gtFine/val/%s/%s_gtFine_color.png' % (city, k), syn.png(labels[k]))
     return img_zip, label_zip, imgs, labels
 
 

@@ -6,7 +6,6 @@ import importlib
 import inspect
 import json
 import os
-import re
 import subprocess
 import sys
 
@@ -15,6 +14,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import segnet_train_synth as syn  # noqa: E402
+
 segnet = importlib.import_module('superpixel-align_amd.segnet')
 st = importlib.import_module('superpixel-align_amd.segnet_train')
 engine = importlib.import_module('superpixel-align_amd.engine')
@@ -32,16 +34,10 @@ def test_abi_rows_equal_float32_rows(spa):
         assert P['spa_segnet_%s_f16x3' % s] == P['spa_segnet_%s' % s]
 
 
-def _declaration(header, name):
-    m = re.search(r'\bint\s+%s\s*\(([^;]*)\)\s*;' % name, header)
-    assert m, '%s is not declared' % name
-    return re.sub(r'\s+', ' ', m.group(1)).strip()
-
-
 def test_declared_in_header_with_float32_arguments():
     header = open(os.path.join(ROOT, 'include', 'spalign.h')).read()
     for s in STAGES:
-        assert _declaration(header, 'spa_segnet_%s_f16x3' % s) == _declaration(header, 'spa_segnet_%s' % s)
+        assert syn.declaration(header, 'spa_segnet_%s_f16x3' % s) == syn.declaration(header, 'spa_segnet_%s' % s)
 
 
 def test_library_exports_f16x3_entry_points(spa):

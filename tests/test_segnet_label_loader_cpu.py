@@ -3,7 +3,6 @@ superpixel-align_amd/segnet_loader.py LabelLoader): the loader with the host sta
 get_raw, the members that send a batch down the host path, the worker task, the slab helper shared with TrainLoader,
 cleanup, the flags of the three drivers, and the small /dev/shm fall-back of save_labels."""
 import importlib
-import io
 import json
 import os
 import subprocess
@@ -33,47 +32,6 @@ rtr = importlib.import_module('utils.run_train_rounds')
 H, W = 32, 64
 
 
-def _png(a, mode=None):
-    from PIL import Image
-    buf = io.BytesIO()
-    im = Image.fromarray(a)
-    if mode == 'P':
-        im = im.convert('P', palette=Image.ADAPTIVE, colors=16)
-    im.save(buf, format='PNG')
-    return buf.getvalue()
-
-
-def _rewrite(src, dst, changes):
-    """a copy of the zip with member k replaced by changes[k](its bytes)"""
-    with zipfile.ZipFile(src) as zi, zipfile.ZipFile(dst, 'w') as zo:
-        for k, name in enumerate(zi.namelist()):
-            data = zi.read(name)
-            zo.writestr(name, changes[k](data) if k in changes else data)
-    return dst
-
-
-def _decoded(data):
-    from PIL import Image
-    with Image.open(io.BytesIO(data)) as f:
-        return np.asarray(f)
-
-
-def _shm_names():
-    return set(os.listdir('/dev/shm')) if os.path.isdir('/dev/shm') else set()
-
-
-def _alive(pid):
-    try:
-        os.kill(pid, 0)
-    except OSError:
-        return False
-    try:
-        with open('/proc/%d/stat' % pid) as f:
-            return f.read().rsplit(')', 1)[1].split()[0] != 'Z'
-    except OSError:
-        return False
-
-
 @pytest.fixture(scope='module')
 def data(tmp_path_factory):
     root = str(tmp_path_factory.mktemp('label_loader'))
@@ -94,7 +52,7 @@ def _run(ds, indices, batch=2, depth=2, **kw):
 # ------------------------------------------------------------------------------- the loader
 def test_loader_yields_get_raw_in_order(data):
     ds = data['ds']
-    before = _shm_names()
+    before = syn.shm_names()
     first, again, n_host, pids = _run(ds, range(1, 5), keep_ids=True)
     assert [b.indices for b in first] == [[1, 2], [3, 4]] == [b.indices for b in again]
     assert n_host == 0 and 1 <= len(pids) <= 2
@@ -108,7 +66,7 @@ def test_loader_yields_get_raw_in_order(data):
                 assert np.array_equal(segnet.label_mask(b.label_ids[j]), label)
                 assert np.array_equal(b.ids_host[j], b.label_ids[j])
     assert (first[0].label_ids[:, :4] == 0).all()           # the synthetic labels' ignored rows are ids, not classes
-    assert _shm_names() == before and not any(_alive(p) for p in pids)
+    assert syn.shm_names() == before and not any(syn.alive(p) for p in pids)
 
 
 def test_short_last_batch_and_depth_rule(data):
@@ -128,14 +86,15 @@ def test_other_modes_and_shapes_mark_their_batch_only(data, tmp_path, what):
     imgs, labs = z[2], z[3]
     k = 3                                                   # index 3: the second batch of range(1, 5)
     if what == 'palette_frame':
-        imgs = _rewrite(z[2], str(tmp_path / 'i.zip'), {k: lambda d: _png(_decoded(d), 'P')})
+        imgs = syn.rewrite(z[2], str(tmp_path / 'i.zip'), {k: lambda d: syn.png(syn.decoded(d), 'P')})
     elif what == 'rgba_frame':
-        imgs = _rewrite(z[2], str(tmp_path / 'i.zip'),
-                        {k: lambda d: _png(np.dstack([_decoded(d), np.full((H, W), 200, np.uint8)]))})
+        imgs = syn.rewrite(z[2], str(tmp_path / 'i.zip'),
+                           {k: lambda d: syn.png(np.dstack([syn.decoded(d), np.full((H, W), 200, np.uint8)]))})
     elif what == 'other_size_frame':
-        imgs = _rewrite(z[2], str(tmp_path / 'i.zip'), {k: lambda d: _png(np.zeros((H + 8, W + 16, 3), np.uint8))})
+        imgs = syn.rewrite(z[2], str(tmp_path / 'i.zip'),
+                           {k: lambda d: syn.png(np.zeros((H + 8, W + 16, 3), np.uint8))})
     else:
-        labs = _rewrite(z[3], str(tmp_path / 'l.zip'), {k: lambda d: _png(np.dstack([_decoded(d)] * 3))})
+        labs = syn.rewrite(z[3], str(tmp_path / 'l.zip'), {k: lambda d: syn.png(np.dstack([syn.decoded(d)] * 3))})
     ds = segnet.ZippedCityscapesRoadDataset(imgs, labs, (H // 2, W // 2))
     first, again, n_host, _ = _run(ds, range(1, 5))
     assert [b.host for b in first] == [False, True] == [b.host for b in again] and n_host == 2
@@ -147,14 +106,14 @@ def test_other_modes_and_shapes_mark_their_batch_only(data, tmp_path, what):
 
 
 def test_close_twice_and_after_a_failed_constructor(data, monkeypatch):
-    before = _shm_names()
+    before = syn.shm_names()
     loader = sl.LabelLoader(data['ds'], range(6), 2, 2, sl.HostLabelStage())
     pids = loader.worker_pids
     it = loader.batches()
     next(it)                                                # batches in flight when it is closed
     loader.close()
     loader.close()
-    assert _shm_names() == before and not any(_alive(p) for p in pids)
+    assert syn.shm_names() == before and not any(syn.alive(p) for p in pids)
 
     class Failing(sl.HostLabelStage):
         n = 0
@@ -166,11 +125,11 @@ def test_close_twice_and_after_a_failed_constructor(data, monkeypatch):
             return sl.HostLabelStage.register(self, shm)
     with pytest.raises(RuntimeError, match='no second slab'):
         sl.LabelLoader(data['ds'], range(6), 2, 2, Failing())
-    assert _shm_names() == before
+    assert syn.shm_names() == before
     monkeypatch.setattr(sl, '_shm_free', lambda: 1 << 20)
     with pytest.raises(cli.ShmTooSmall, match='label loader'):
         sl.LabelLoader(data['ds'], range(6), 2, 2, sl.HostLabelStage())
-    assert _shm_names() == before
+    assert syn.shm_names() == before
 
 
 # ------------------------------------------------------------------------------- the worker task
@@ -178,7 +137,7 @@ def test_png_task_checks_shape_and_mode(data):
     z = data['z']
     with zipfile.ZipFile(z[2]) as zi, zipfile.ZipFile(z[3]) as zl:
         frame, label = zi.namelist()[0], zl.namelist()[0]
-        want_f, want_l = _decoded(zi.read(frame)), _decoded(zl.read(label))
+        want_f, want_l = syn.decoded(zi.read(frame)), syn.decoded(zl.read(label))
     shm = shared_memory.SharedMemory(create=True, size=H * W * 4 + 64)
     try:
         buf = np.frombuffer(shm.buf, dtype=np.uint8)
@@ -214,7 +173,7 @@ def test_worker_module_imports_nothing_heavy():
 # ------------------------------------------------------------------------------- the shared helper
 def test_two_loaders_share_one_pool(data):
     z = data['z']
-    before = _shm_names()
+    before = syn.shm_names()
     train = st.ZippedEstimatedCityscapesDataset(z[0], z[1], (H // 2, W // 2), False, False)
     np.random.seed(0)
     tl = sl.TrainLoader(train, np.arange(4), st.ShuffledIterator(4, 2), 2, sl.HostStage(train))
@@ -226,17 +185,17 @@ def test_two_loaders_share_one_pool(data):
         img, lab, _ = tl.next()
         assert img.shape == (2, 3, H // 2, W // 2)
         ll.close()                                          # the other loader goes on, on the same workers
-        assert all(_alive(p) for p in tl.worker_pids)
+        assert all(syn.alive(p) for p in tl.worker_pids)
         tl.next()
         ll = sl.LabelLoader(data['ds'], range(6), 2, 2, sl.HostLabelStage(), pool=tl.workers)
         tl.close()                                          # and the other way round
         assert [b.indices for b in ll.batches()] == [[0, 1], [2, 3], [4, 5]]
-        assert all(_alive(p) for p in ll.worker_pids)
+        assert all(syn.alive(p) for p in ll.worker_pids)
     finally:
         if ll is not None:
             ll.close()
         tl.close()
-    assert _shm_names() == before and not any(_alive(p) for p in tl.worker_pids)
+    assert syn.shm_names() == before and not any(syn.alive(p) for p in tl.worker_pids)
 
 
 # ------------------------------------------------------------------------------- flags
@@ -327,7 +286,7 @@ def test_small_shm_takes_the_plain_loop(data, tmp_path, monkeypatch, capsys):
     with open(str(param_dir / 'args.txt'), 'w') as f:
         json.dump({'model': 'basic', 'input_shape': [H // 2, W // 2], 'batchsize': 2}, f)
     z = data['z']
-    before = _shm_names()
+    before = syn.shm_names()
     stats = {}
     out = str(tmp_path / 'out')
     lfs.save_labels(str(param_dir), 1, 0, z[2], z[3], out, 0, 5, False, [H, W], save_each=True, figure=False,
@@ -337,7 +296,7 @@ def test_small_shm_takes_the_plain_loop(data, tmp_path, monkeypatch, capsys):
     assert printed.rstrip().endswith('; the images are decoded on the host')
     assert eng.confusions == 5 and eng.label_evals == 0 and list(stats) == ['loop_s']
     assert len(open(os.path.join(out, 'result.json')).readlines()) == 5
-    assert len([f for f in os.listdir(out) if f.endswith('.npy')]) == 10 and _shm_names() == before
+    assert len([f for f in os.listdir(out) if f.endswith('.npy')]) == 10 and syn.shm_names() == before
 
 
 # ------------------------------------------------------------------------------- the loader run's order, no GPU
@@ -399,10 +358,10 @@ def test_loader_run_keeps_the_plain_loops_outputs_and_order(data, tmp_path, monk
         json.dump({'model': 'basic', 'input_shape': [H // 2, W // 2], 'batchsize': 2}, f)
     z = data['z']
     rng = np.random.default_rng(2)
-    fb = _rewrite(z[2], str(tmp_path / 'fb.zip'),
-                  {2: lambda b: _png(rng.integers(0, 256, (H + 16, W + 16, 3), dtype=np.uint8)),
-                   4: lambda b: _png(_decoded(b)[:, :, 1].copy())})
-    bad = _rewrite(z[3], str(tmp_path / 'bad.zip'), {3: lambda b: _png(_decoded(b)[:H - 8].copy())})
+    fb = syn.rewrite(z[2], str(tmp_path / 'fb.zip'),
+                     {2: lambda b: syn.png(rng.integers(0, 256, (H + 16, W + 16, 3), dtype=np.uint8)),
+                      4: lambda b: syn.png(syn.decoded(b)[:, :, 1].copy())})
+    bad = syn.rewrite(z[3], str(tmp_path / 'bad.zip'), {3: lambda b: syn.png(syn.decoded(b)[:H - 8].copy())})
 
     def save(out, procs, imgs=z[2], labs=z[3], **kw):
         return lfs.save_labels(str(param_dir), 7, 0, imgs, labs, out, 0, 5, False, [H, W], figure=False, batchsize=2,
@@ -415,7 +374,7 @@ def test_loader_run_keeps_the_plain_loops_outputs_and_order(data, tmp_path, monk
         got = [json.loads(l) for l in open(os.path.join(out, 'result.json'))]
         assert all(l.pop('out_dir') == out for l in got)
         return got
-    before = _shm_names()
+    before = syn.shm_names()
     for name, imgs, n_host in (('same', z[2], 0), ('fallback', fb, 2)):
         a, b = str(tmp_path / (name + '_plain')), str(tmp_path / (name + '_loader'))
         stats = {}
@@ -443,4 +402,4 @@ def test_loader_run_keeps_the_plain_loops_outputs_and_order(data, tmp_path, monk
     assert files(str(tmp_path / 'bad_plain')) == files(str(tmp_path / 'bad_loader'))
     assert len(files(str(tmp_path / 'bad_plain'))) == 6
     assert lines(str(tmp_path / 'bad_plain')) == lines(str(tmp_path / 'bad_loader'))
-    assert _shm_names() == before
+    assert syn.shm_names() == before

@@ -34,10 +34,6 @@ SHAPES = [((256, 512), (128, 256)), ((97, 131), (40, 56)), ((40, 56), (97, 131))
           ((203, 77), (64, 48))]
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 @pytest.mark.parametrize('src,dst', SHAPES)
 def test_float_bicubic_restatement_equals_pillow(src, dst):
     """pil_bicubic_coeffs + the two-pass float64 accumulation (what spa_segnet_train_input runs) against Pillow's mode
@@ -48,7 +44,7 @@ def test_float_bicubic_restatement_equals_pillow(src, dst):
         ref = st.resize_bicubic_float(img, dst)
         got = st.pil_resize_float(img, dst)
         assert got.dtype == np.float32 and got.shape == ref.shape
-        assert int((_bits(got) != _bits(ref)).sum()) == 0
+        assert int((syn.bits(got) != syn.bits(ref)).sum()) == 0
 
 
 def test_coefficient_tables_are_bounded_and_normalised():
@@ -70,12 +66,6 @@ def test_nearest_index_table(n_src, n_dst):
 
 
 # ------------------------------------------------------------------------------- the label task
-def _npy(a):
-    buf = io.BytesIO()
-    np.save(buf, a)
-    return buf.getvalue()
-
-
 def test_label_task_reads_masks_and_scores(tmp_path):
     rng = np.random.default_rng(3)
     mask = rng.random((20, 36)) > 0.5
@@ -84,12 +74,12 @@ def test_label_task_reads_masks_and_scores(tmp_path):
     wide = rng.integers(0, 5, (20, 36)).astype(np.int64)
     zfn = str(tmp_path / 'labels.zip')
     with zipfile.ZipFile(zfn, 'w', zipfile.ZIP_STORED) as zf:
-        zf.writestr('d/a_leftImg8bit.npy', _npy(mask))
-        zf.writestr('d/a_leftImg8bit_scores.npy', _npy(scores))
+        zf.writestr('d/a_leftImg8bit.npy', syn.npy(mask))
+        zf.writestr('d/a_leftImg8bit_scores.npy', syn.npy(scores))
     with zipfile.ZipFile(zfn, 'a', zipfile.ZIP_DEFLATED) as zf:
-        zf.writestr('d/b_leftImg8bit.npy', _npy(mask8))
-        zf.writestr('d/c_leftImg8bit.npy', _npy(wide))
-        zf.writestr('d/f_leftImg8bit_scores.npy', _npy(np.asfortranarray(scores)))
+        zf.writestr('d/b_leftImg8bit.npy', syn.npy(mask8))
+        zf.writestr('d/c_leftImg8bit.npy', syn.npy(wide))
+        zf.writestr('d/f_leftImg8bit_scores.npy', syn.npy(np.asfortranarray(scores)))
     shm = shared_memory.SharedMemory(create=True, size=1 << 16)
     try:
         buf = np.frombuffer(shm.buf, dtype=np.uint8)
@@ -122,7 +112,7 @@ def _soft_zip(z, path, C=2, seed=5):
         for name in zl.namelist():
             m = np.load(io.BytesIO(zl.read(name)))
             zo.writestr(name, zl.read(name))
-            zo.writestr(name[:-len('.npy')] + '_scores.npy', _npy(rng.random((C,) + m.shape).astype(np.float32)))
+            zo.writestr(name[:-len('.npy')] + '_scores.npy', syn.npy(rng.random((C,) + m.shape).astype(np.float32)))
     return path
 
 
@@ -159,25 +149,9 @@ def _compare(plain, got):
     assert len(plain) == len(got)
     for (pi, pl, ps), (gi, gl, gs) in zip(plain, got):
         assert gi.dtype == np.float32 and gi.shape == pi.shape and gl.dtype == pl.dtype and gl.shape == pl.shape
-        assert np.array_equal(_bits(gi), _bits(pi))
+        assert np.array_equal(syn.bits(gi), syn.bits(pi))
         assert np.array_equal(gl, pl)
         _same_state(ps, gs)
-
-
-def _shm_names():
-    return set(os.listdir('/dev/shm')) if os.path.isdir('/dev/shm') else set()
-
-
-def _alive(pid):
-    try:
-        os.kill(pid, 0)
-    except OSError:
-        return False
-    try:
-        with open('/proc/%d/stat' % pid) as f:
-            return f.read().rsplit(')', 1)[1].split()[0] != 'Z'
-    except OSError:
-        return False
 
 
 @pytest.mark.parametrize('soft,random', [(False, True), (True, True), (False, False)])
@@ -188,14 +162,14 @@ def test_loader_yields_the_plain_loop(tmp_path, soft, random):
     z = syn.write(str(tmp_path / 'data'), 7, 1, 48, 96)
     label_zip = _soft_zip(z, str(tmp_path / 'soft.zip')) if soft else z[1]
     ds = st.ZippedEstimatedCityscapesDataset(z[0], label_zip, (32, 64), random, soft)
-    before = _shm_names()
+    before = syn.shm_names()
     plain = _plain(ds, 7, 3, 9, seed=11)
     assert plain[-1][2][0]['epoch'] >= 3
     got, n_host, pids = _loaded(ds, 7, 3, 9, seed=11)
     _compare(plain, got)
     assert n_host == 0 and len(pids) >= 1
-    assert not any(_alive(p) for p in pids)
-    assert _shm_names() == before
+    assert not any(syn.alive(p) for p in pids)
+    assert syn.shm_names() == before
 
 
 def test_equal_size_frames_pass_through(tmp_path):
@@ -224,7 +198,7 @@ def test_off_size_frame_takes_the_host_path(tmp_path):
             zo.writestr(name, data)
     with zipfile.ZipFile(z[1]) as zl, zipfile.ZipFile(labs, 'w') as zo:
         for k, name in enumerate(zl.namelist()):
-            zo.writestr(name, _npy(odd_mask) if k == 3 else zl.read(name))
+            zo.writestr(name, syn.npy(odd_mask) if k == 3 else zl.read(name))
     ds = st.ZippedEstimatedCityscapesDataset(imgs, labs, (32, 64), True, False)
     got, n_host, _ = _loaded(ds, 5, 2, 8, seed=4)
     _compare(_plain(ds, 5, 2, 8, seed=4), got)
@@ -238,11 +212,11 @@ def test_small_shm_is_refused_before_any_draw(tmp_path, monkeypatch):
     np.random.seed(0)
     it = st.ShuffledIterator(4, 2)
     state = np.random.get_state()
-    before = _shm_names()
+    before = syn.shm_names()
     with pytest.raises(cli.ShmTooSmall):
         sl.TrainLoader(ds, np.arange(4), it, 2, sl.HostStage(ds))
     assert np.array_equal(np.random.get_state()[1], state[1]) and np.random.get_state()[2] == state[2]
-    assert it.current_position == 0 and _shm_names() == before
+    assert it.current_position == 0 and syn.shm_names() == before
 
 
 def test_driver_says_so_once_and_goes_on_without_the_loader(tmp_path, monkeypatch, capsys):
@@ -295,13 +269,13 @@ def test_workers_do_not_outlive_a_killed_trainer(tmp_path):
         line = p.stdout.readline()
         pids = [int(v) for v in line.split()]
         assert pids, p.stderr.read()[-2000:]
-        assert all(_alive(q) for q in pids)
+        assert all(syn.alive(q) for q in pids)
         p.send_signal(signal.SIGKILL)
         p.wait(timeout=30)
         deadline = time.time() + 30
-        while time.time() < deadline and any(_alive(q) for q in pids):
+        while time.time() < deadline and any(syn.alive(q) for q in pids):
             time.sleep(0.1)
-        assert not any(_alive(q) for q in pids)
+        assert not any(syn.alive(q) for q in pids)
     finally:
         if p.poll() is None:
             p.kill()

@@ -14,6 +14,9 @@ torch = pytest.importorskip('torch')
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import segnet_train_synth as syn  # noqa: E402
+
 segnet = importlib.import_module('superpixel-align_amd.segnet')
 st = importlib.import_module('superpixel-align_amd.segnet_train')
 train_segnet = importlib.import_module('train_segnet')
@@ -114,24 +117,6 @@ def test_rounding_hook_in_reference_step():
     assert torch.equal(gx, hx) and torch.equal(gw, hw)
 
 
-class _FakeTrainer(object):
-    """what save_snapshot reads from a trainer, without a GPU"""
-
-    def __init__(self, dtype=None):
-        self._p = st.init_params(1)
-        self.opt = st.MomentumSGD(0.01)
-        self.opt.t = 3
-        self.opt.state = {'conv1/W': {'v': torch.ones((64, 3, 7, 7))}}
-        if dtype is not None:
-            self.dtype = dtype
-
-    def params_numpy(self):
-        out = dict(self._p)
-        for n in segnet.LAYERS:
-            out[n + '_bn/N'] = np.asarray(2)
-        return out
-
-
 @pytest.mark.parametrize('dtype', ['fp32', 'bf16'])
 def test_snapshot_round_trips_dtype(tmp_path, dtype):
     d = tmp_path / 'run'
@@ -139,7 +124,7 @@ def test_snapshot_round_trips_dtype(tmp_path, dtype):
     json.dump({'model': 'basic', 'input_shape': [32, 64], 'dtype': dtype}, open(str(d / 'args.txt'), 'w'))
     it = st.ShuffledIterator(5, 2)
     path = str(d / 'snapshot_iter_10')
-    st.save_snapshot(path, _FakeTrainer(dtype), 10, 0.01, it.state())
+    st.save_snapshot(path, syn.FakeTrainer(st.init_params(1), 3, 2, dtype=dtype), 10, 0.01, it.state())
     assert st.snapshot_dtype(path) == dtype
     params, state, t, lr, iteration, its, rnd = st.load_snapshot_state(path)
     assert (t, lr, iteration) == (3, 0.01, 10)
@@ -151,7 +136,7 @@ def test_snapshot_round_trips_dtype(tmp_path, dtype):
 
 def test_snapshot_without_dtype_is_fp32(tmp_path):
     path = str(tmp_path / 'snapshot_iter_1')
-    st.save_snapshot(path, _FakeTrainer(), 1, 0.01, st.ShuffledIterator(3, 1).state())
+    st.save_snapshot(path, syn.FakeTrainer(st.init_params(1), 3, 2), 1, 0.01, st.ShuffledIterator(3, 1).state())
     assert st.snapshot_dtype(path) == 'fp32'
     with np.load(path) as z:
         np.savez(str(tmp_path / 'old.npz'), **{k: z[k] for k in z.files if k != st.DTYPE_KEY})

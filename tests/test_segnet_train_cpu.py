@@ -15,6 +15,9 @@ torch = pytest.importorskip('torch')
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import segnet_train_synth as syn  # noqa: E402
+
 segnet = importlib.import_module('superpixel-align_amd.segnet')
 st = importlib.import_module('superpixel-align_amd.segnet_train')
 cli = importlib.import_module('superpixel-align_amd.cli')
@@ -167,29 +170,13 @@ def _tiny_trainer_state():
     return p
 
 
-class _FakeTrainer(object):
-    """what save_snapshot reads from a trainer, without a GPU"""
-
-    def __init__(self, p):
-        self._p = p
-        self.opt = st.MomentumSGD(0.01)
-        self.opt.t = 7
-        self.opt.state = {'conv1/W': {'v': torch.ones((64, 3, 7, 7))}}
-
-    def params_numpy(self):
-        out = dict(self._p)
-        for n in segnet.LAYERS:
-            out[n + '_bn/N'] = np.asarray(3)
-        return out
-
-
 def test_snapshot_loads_with_segnet(tmp_path):
     p = _tiny_trainer_state()
     d = tmp_path / 'run'
     d.mkdir()
     json.dump({'model': 'basic', 'input_shape': [32, 64]}, open(str(d / 'args.txt'), 'w'))
     it = st.ShuffledIterator(5, 2)
-    st.save_snapshot(str(d / 'snapshot_iter_20'), _FakeTrainer(p), 20, 0.001, it.state())
+    st.save_snapshot(str(d / 'snapshot_iter_20'), syn.FakeTrainer(p, 7, 3), 20, 0.001, it.state())
     args, snap, params = segnet.load_snapshot(str(d), 20)
     for k in st.PARAM_KEYS + st.STAT_KEYS:
         assert np.array_equal(params[k], p[k]), k

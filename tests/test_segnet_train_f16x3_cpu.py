@@ -5,7 +5,6 @@ ones, and utils/run_train_rounds.py passes the flag to the training children onl
 import importlib
 import json
 import os
-import re
 import sys
 
 import numpy as np
@@ -16,6 +15,9 @@ torch = pytest.importorskip('torch')
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import segnet_train_synth as syn  # noqa: E402
+
 segnet = importlib.import_module('superpixel-align_amd.segnet')
 st = importlib.import_module('superpixel-align_amd.segnet_train')
 engine = importlib.import_module('superpixel-align_amd.engine')
@@ -66,25 +68,6 @@ def test_bf16_refusal_before_any_engine(monkeypatch):
         st.SegNetTrainer(st.init_params(0), st.MomentumSGD(), st.softmax_cross_entropy, split_planes=True)
 
 
-class _FakeTrainer(object):
-    """what save_snapshot reads from a trainer, without a GPU"""
-
-    def __init__(self, split_planes=None):
-        self._p = st.init_params(1)
-        self.opt = st.MomentumSGD(0.01)
-        self.opt.t = 3
-        self.opt.state = {'conv1/W': {'v': torch.ones((64, 3, 7, 7))}}
-        self.dtype = 'fp32'
-        if split_planes is not None:
-            self.split_planes = split_planes
-
-    def params_numpy(self):
-        out = dict(self._p)
-        for n in segnet.LAYERS:
-            out[n + '_bn/N'] = np.asarray(2)
-        return out
-
-
 def _keys(path):
     with np.load(path) as z:
         return set(z.files)
@@ -98,7 +81,8 @@ def test_snapshot_entries(tmp_path):
         d.mkdir()
         json.dump({'model': 'basic', 'input_shape': [32, 64], 'dtype': 'fp32'}, open(str(d / 'args.txt'), 'w'))
         paths[tag] = str(d / 'snapshot_iter_10')
-        st.save_snapshot(paths[tag], _FakeTrainer(sp), 10, 0.01, it.state())
+        attrs = dict(dtype='fp32') if sp is None else dict(dtype='fp32', split_planes=sp)
+        st.save_snapshot(paths[tag], syn.FakeTrainer(st.init_params(1), 3, 2, **attrs), 10, 0.01, it.state())
     assert _keys(paths['off']) == _keys(paths['plain'])               # a default run keeps today's entries
     assert st.SPLIT_PLANES_KEY not in _keys(paths['plain'])
     assert _keys(paths['on']) == _keys(paths['plain']) | {st.SPLIT_PLANES_KEY}
@@ -123,16 +107,11 @@ def test_abi_rows_equal_float32_rows(spa):
         assert callable(getattr(engine.Engine, 'segnet_train_%s_f16x3' % p))
 
 
-def _declaration(header, name):
-    m = re.search(r'\bint\s+%s\s*\(([^;]*)\)\s*;' % name, header)
-    assert m, '%s is not declared' % name
-    return re.sub(r'\s+', ' ', m.group(1)).strip()
-
-
 def test_declared_in_header_with_float32_arguments():
     header = open(os.path.join(ROOT, 'include', 'spalign.h')).read()
     for p in PASSES:
-        assert _declaration(header, 'spa_segnet_train_%s_f16x3' % p) == _declaration(header, 'spa_segnet_train_%s' % p)
+        assert syn.declaration(header, 'spa_segnet_train_%s_f16x3' % p) == \
+            syn.declaration(header, 'spa_segnet_train_%s' % p)
 
 
 def test_library_exports_f16x3_entry_points(spa):
