@@ -256,11 +256,9 @@ def save_labels(param_dir, iteration, gpu, img_zip_fn, label_zip_fn, out_dir,
     loader = None
     if int(loader_procs) > 0 and end_index > start_index:
         sl = importlib.import_module('superpixel-align_amd.segnet_loader')
-        try:
-            loader = sl.LabelLoader(d, range(start_index, end_index), batchsize, int(loader_procs),
-                                    sl.DeviceLabelStage(eng), keep_ids=figure)
-        except cli.ShmTooSmall as e:
-            print('--loader_procs: %s; the images are decoded on the host' % e, flush=True)
+        loader = sl.open_or_none(lambda: sl.LabelLoader(d, range(start_index, end_index), batchsize, int(loader_procs),
+                                                        sl.DeviceLabelStage(eng), keep_ids=figure),
+                                 '--loader_procs: %s; the images are decoded on the host')
     times = {'loader_wait_s': 0.0, 'device_wait_s': 0.0, 'output_s': 0.0}
     t_loop = time.perf_counter()
     if loader is None:

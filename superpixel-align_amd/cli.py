@@ -5,7 +5,8 @@
 
 Flags, defaults (including the two dead flags), the "keep the batch size" loop, the NPY /
 result.json / PNG naming and contents are the reference's; additions are optional flags
-(--arch, --dtype, --drn_weights, --pool_mode, --mean_sampling, --no_figure, --balanced).
+(--arch, --dtype, --drn_weights, --pool_mode, --mean_sampling, --no_figure, --balanced, --io_threads, --decode_procs:
+ProcessDecoder below, on the slabs and workers of slabs.py).
 Under `python -m torch.distributed.run --nproc-per-node N` the labelled driver shards the image
 range like utils/create_*_labels.sh does and rank 0 writes result.json after one all_gather.
 """
@@ -23,9 +24,11 @@ os.environ.setdefault('MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD', '0')
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from . import decode_worker
 from . import dist as spdist
 from . import ops
 from .pipeline import LabelPipeline
+from .slabs import Layout, PinnedSlabs, ShmTooSmall, Slabs, open_or_none
 
 # (flag, kwargs) shared by both drivers, in the reference's order
 _COMMON_FLAGS = [
@@ -227,59 +230,21 @@ class PinnedRing(object):
         return t
 
 
-class ShmTooSmall(RuntimeError):
-    """/dev/shm cannot hold the decode slabs: the caller falls back to the decode threads."""
-
-
 class ProcessDecoder(object):
     """Batches of PNGs decoded by worker processes into shared-memory slabs that are registered as pinned host memory
-    (decode_worker.py).  take(idx) -> (images uint8 (B,H,W,3) device tensor, labels uint8 (B,H,W) device tensor, list of
-    label arrays on the host) enqueued on the current stream, or None when a frame of the batch has another size
-    than the first image of the run (the caller then decodes that batch on its threads)."""
+    (slabs.py, decode_worker.py).  take(idx) -> (images uint8 (B,H,W,3) device tensor, labels uint8 (B,H,W) device
+    tensor, list of label arrays on the host) enqueued on the current stream, or None when a frame of the batch has
+    another size than the first image of the run (the caller then decodes that batch on its threads).  Raises
+    ShmTooSmall where /dev/shm cannot hold the slabs (30 full-size frames need 3 x 250 MB)."""
 
     def __init__(self, imgs_ds, labels_ds, batch, n_procs, device, depth=3, host_labels=False):
-        import multiprocessing as mp
-        from concurrent.futures import ProcessPoolExecutor
-        from multiprocessing import shared_memory
-        from . import decode_worker
-        self._w = decode_worker
-        self.imgs, self.labels, self.device = imgs_ds, labels_ds, device
-        first = imgs_ds.get_raw(0)
-        gt0 = labels_ds.get_gray(0)
-        self.ishape, self.gshape = tuple(first.shape), tuple(gt0.shape)
-        self.B, self.host_labels = batch, host_labels
-        self.ibytes = int(np.prod(self.ishape))
-        self.gbytes = int(np.prod(self.gshape))
-        slab = batch * (self.ibytes + self.gbytes)
-        # the slabs live in /dev/shm: on a tmpfs smaller than they are (a container's default is 64 MB; 30 full-size frames
-        # need 3 x 250 MB) SharedMemory(create=True) still succeeds and the workers die with SIGBUS on their first write
-        try:
-            st = os.statvfs('/dev/shm')
-            free = st.f_bavail * st.f_frsize
-        except OSError:
-            free = None
-        if free is not None and free < depth * slab + (16 << 20):
-            raise ShmTooSmall('/dev/shm has %d MB free, the decode slabs need %d MB' % (free >> 20, (depth * slab) >> 20))
-        self.slots = []
-        self.pool = None
-        try:
-            for _ in range(depth):
-                shm = shared_memory.SharedMemory(create=True, size=slab)
-                slot = dict(shm=shm, t=None, pinned=False, ev=None)
-                self.slots.append(slot)
-                slot['t'] = t = torch.frombuffer(shm.buf, dtype=torch.uint8)
-                try:
-                    rc = torch.cuda.cudart().cudaHostRegister(t.data_ptr(), slab, 0)
-                    slot['pinned'] = rc is None or int(rc) == 0
-                except Exception:
-                    slot['pinned'] = False                  # pageable slab: the upload is staged, still correct
-            self.k = 0
-            # spawn, not fork: this process has initialised the GPU
-            self.pool = ProcessPoolExecutor(max_workers=n_procs, mp_context=mp.get_context('spawn'))
-            list(self.pool.map(decode_worker.warm, range(n_procs)))
-        except BaseException:
-            self.close()                                # unregister and unlink what exists so far
-            raise
+        self.imgs, self.labels, self.device, self.host_labels = imgs_ds, labels_ds, device, host_labels
+        self.ishape, self.gshape = tuple(imgs_ds.get_raw(0).shape), tuple(labels_ds.get_gray(0).shape)
+        self.layout = Layout(batch, [('frames', self.ishape, np.uint8), ('labels', self.gshape, np.uint8)])
+        self.stage = PinnedSlabs('--decode_procs')
+        self.slabs = Slabs('the decode', self.layout.nbytes, depth, n_procs, self.stage)
+        self.worker_pids = self.slabs.worker_pids
+        self.k = 0
 
     def _src(self, ds, i):
         p = ds._paths[i]
@@ -289,45 +254,24 @@ class ProcessDecoder(object):
         return p
 
     def take(self, idx):
-        slot = self.slots[self.k % len(self.slots)]
+        slot = self.slabs.slots[self.k % len(self.slabs.slots)]
         self.k += 1
-        if slot['ev'] is not None:
-            slot['ev'].synchronize()                   # the slab's last upload has finished
-        n = len(idx)
-        name = slot['shm'].name
-        tasks = [(name, j * self.ibytes, self.ishape, self._src(self.imgs, i)) for j, i in enumerate(idx)]
-        tasks += [(name, self.B * self.ibytes + j * self.gbytes, self.gshape, self._src(self.labels, i)) for j, i in enumerate(idx)]
-        shapes = list(self.pool.map(self._w.decode_into, tasks, chunksize=1))
+        self.stage.wait(slot['handle'])                # the slab's last upload has finished
+        n, name, at = len(idx), slot['shm'].name, self.layout.offset
+        tasks = [(name, at('frames', j), self.ishape, self._src(self.imgs, i)) for j, i in enumerate(idx)]
+        tasks += [(name, at('labels', j), self.gshape, self._src(self.labels, i)) for j, i in enumerate(idx)]
+        shapes = list(self.slabs.workers.executor.map(decode_worker.decode_into, tasks, chunksize=1))
         if any(tuple(sh) != (self.ishape if k < n else self.gshape) for k, sh in enumerate(shapes)):
             return None
-        t = slot['t']
-        img_h = t[:n * self.ibytes].view((n,) + self.ishape)
-        gt_h = t[self.B * self.ibytes:self.B * self.ibytes + n * self.gbytes].view((n,) + self.gshape)
+        img_h, gt_h = self.layout.tensor_views(slot['handle']['t'], n)
         img_d = img_h.to(self.device, non_blocking=True)
         gt_d = gt_h.to(self.device, non_blocking=True)
-        slot['ev'] = torch.cuda.Event()
-        slot['ev'].record(torch.cuda.current_stream(self.device))
+        self.stage.uploaded(slot['handle'], torch.cuda.current_stream(self.device))
         # the figure writer wants the labels on the host: copies, the slab comes round again before it runs
         return img_d, gt_d, [np.array(gt_h[j].numpy()) if self.host_labels else None for j in range(n)]
 
     def close(self):
-        if self.pool is not None:
-            self.pool.shutdown(wait=True, cancel_futures=True)
-            self.pool = None
-        for s in self.slots:
-            if s.get('t') is not None:
-                if s.get('pinned'):
-                    try:
-                        torch.cuda.cudart().cudaHostUnregister(s['t'].data_ptr())
-                    except Exception:
-                        pass
-                s['t'] = None
-            try:
-                s['shm'].close()
-                s['shm'].unlink()
-            except Exception:
-                pass
-        self.slots = []
+        self.slabs.close()
 
 
 class ImageList(object):
@@ -675,11 +619,9 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
 
         decoder_lock = threading.Lock()
         if use_async and have_gpu and getattr(args, 'decode_procs', 0) > 0 and not args.host_resize and ranges:
-            try:
-                decoder = ProcessDecoder(imgs_ds, labels_ds, args.batchsize, args.decode_procs, ops.engine().device,
-                                         host_labels=not args.no_figure)
-            except ShmTooSmall as exc:
-                print('--decode_procs: %s; decoding on the %d io threads instead' % (exc, args.io_threads), file=sys.stderr)
+            decoder = open_or_none(lambda: ProcessDecoder(imgs_ds, labels_ds, args.batchsize, args.decode_procs,
+                                                          ops.engine().device, host_labels=not args.no_figure),
+                                   '--decode_procs: %%s; decoding on the %d io threads instead' % args.io_threads, sys.stderr)
         depth = 2 if use_async else 1
         queue = [loader.submit(load, lo, hi) for lo, hi in ranges[:depth]]
         if use_async:

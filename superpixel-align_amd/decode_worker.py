@@ -1,5 +1,6 @@
-"""PNG decoding in worker PROCESSES for the labelled driver (input stage of batch_spalign_kmeans.py:486-548:
-ResizeImageDataset / ZippedCityscapesRoadDataset decode one PNG per image on the main thread).
+"""The tasks of the decode worker PROCESSES: for the labelled driver (input stage of batch_spalign_kmeans.py:486-548:
+ResizeImageDataset / ZippedCityscapesRoadDataset decode one PNG per image on the main thread) and for the SegNet
+loaders.  The parent's side (slabs, the pool that starts these workers, the ring) is slabs.py.
 
 Threads scale the decode itself (zlib releases the GIL) but every thread still runs PIL's Python-level chunk loop,
 and with 32 of them the main thread — which issues ~400 kernel launches per batch from Python — waits 40-100 ms per

@@ -24,28 +24,22 @@ the draw order use it, with real workers.
 
 LabelLoader feeds the two loops that read a ZippedCityscapesRoadDataset with get_raw (labels_from_segnet.save_labels
 and train_segnet.evaluate, --loader_procs) the same way: frames and raw labelIds bytes, in index order, nothing drawn.
-Both loaders keep their slabs and workers in one helper, Slabs, and may share one WorkerPool.
-"""
-import collections
-import os
 
+Both loaders are a slabs.Ring: the slabs, the workers (one WorkerPool may serve both), the batches in flight and the
+close sequence live there, and the stages' registration, upload, wait and finish in slabs.HostSlabStage and
+slabs.DeviceSlabStage.  What is here is what differs: the draws or the index order, the slab's fields, the test of the
+workers' return values, the host path, and what a stage does with the fields (on_slab).
+"""
 import numpy as np
 
 from . import decode_worker
 from . import segnet_train as st
+from .slabs import DeviceSlabStage, HostSlabStage, Layout, Ring, Slabs, WorkerPool, open_or_none  # noqa: F401
 
 
 def default_depth(n_procs, batchsize):
     """batches in flight: enough image tasks to occupy every worker, plus the batch being uploaded; 3..6"""
     return max(3, min(6, -(-int(n_procs) // max(int(batchsize), 1)) + 1))
-
-
-def _shm_free():
-    try:
-        s = os.statvfs('/dev/shm')
-        return s.f_bavail * s.f_frsize
-    except OSError:
-        return None
 
 
 def _first_shapes(ds):
@@ -61,250 +55,68 @@ def _first_shapes(ds):
     return (H, W, 3), tuple(shape)
 
 
-class HostStage(object):
+def _host_batch(batch):
+    return np.stack([b[0] for b in batch]), np.stack([b[1] for b in batch])
+
+
+class HostStage(HostSlabStage):
     """The device stage's work with get_example's own functions: numpy batches in, numpy batches out."""
 
     def __init__(self, dataset):
         self.ds = dataset
 
-    def register(self, shm):
-        return {'pinned': False}
-
-    def unregister(self, handle):
-        pass
-
-    def wait(self, handle):
-        pass
-
-    def run(self, handle, views, n, random):
-        imgs, labs, shifts, flips = views
+    def on_slab(self, fields):
+        imgs, labs, shifts, flips = fields
         out = []
-        for j in range(n):
+        for j in range(len(imgs)):
             img = imgs[j].astype(np.float32).transpose(2, 0, 1)
             lab = labs[j].astype(np.float32 if self.ds.use_soft_label else np.int32)
             img, lab = self.ds.resized(img, lab)
-            if random:
+            if self.ds.random:
                 out.append(self.ds.augmented(img, lab, shifts[j], bool(flips[j])))
             else:
                 out.append((np.ascontiguousarray(img, np.float32), np.ascontiguousarray(lab)))
-        return self.from_host(out)
+        return _host_batch(out)
 
-    def from_host(self, batch):
-        return np.stack([b[0] for b in batch]), np.stack([b[1] for b in batch])
-
-    def finish(self, out):
-        return out
-
-    def close(self):
-        pass
+    from_host = staticmethod(_host_batch)
 
 
-class DeviceStage(object):
-    """One upload of the slab and the two input kernels on a side stream; finish() makes the current stream wait for
-    the batch's event."""
+class DeviceStage(DeviceSlabStage):
+    """The two input kernels on the uploaded slab, on the side stream."""
 
     def __init__(self, dataset, engine):
-        import torch
-        self.torch, self.ds, self.eng = torch, dataset, engine
-        self.side = torch.cuda.Stream(engine.device)
-        self.warned = False
+        DeviceSlabStage.__init__(self, engine.device, 'segnet_loader')
+        self.ds, self.eng = dataset, engine
 
-    def register(self, shm):
-        torch = self.torch
-        t = torch.frombuffer(shm.buf, dtype=torch.uint8)
-        pinned = False
-        try:
-            rc = torch.cuda.cudart().cudaHostRegister(t.data_ptr(), t.numel(), 0)
-            pinned = rc is None or int(rc) == 0
-        except Exception:
-            pinned = False
-        if not pinned and not self.warned:
-            self.warned = True                              # pageable slabs: same bits, but the upload is a staged copy
-            print('segnet_loader: the slabs could not be registered as pinned host memory; uploads will not overlap '
-                  'the step', flush=True)
-        return {'t': t, 'pinned': pinned, 'ev': None}
-
-    def unregister(self, handle):
-        if handle['pinned']:
-            try:
-                self.torch.cuda.cudart().cudaHostUnregister(handle['t'].data_ptr())
-            except Exception:
-                pass
-        handle['t'] = None
-
-    def wait(self, handle):
-        if handle['ev'] is not None:
-            handle['ev'].synchronize()                      # the slab's last upload has finished
-
-    def run(self, handle, views, n, random):
-        torch = self.torch
-        imgs, labs, shifts, flips = views
-        base = imgs.__array_interface__['data'][0]
-
-        def dev_view(d, a, dtype):
-            off = a.__array_interface__['data'][0] - base
-            return d[off:off + a.nbytes].view(dtype).view(tuple(a.shape))
-
-        end = flips.__array_interface__['data'][0] + flips.nbytes - base
-        with torch.cuda.stream(self.side):
-            d = handle['t'][:end].to(self.eng.device, non_blocking=True)
-            handle['ev'] = torch.cuda.Event()
-            handle['ev'].record(self.side)
-            sh = dev_view(d, shifts[:n], torch.float64) if random else None
-            fl = dev_view(d, flips[:n], torch.uint8) if random else None
-            img = self.eng.segnet_train_input(dev_view(d, imgs[:n], torch.uint8), self.ds.resize_shape, sh, fl)
-            lab = self.eng.segnet_train_label(dev_view(d, labs[:n], getattr(torch, str(labs.dtype))),
-                                              self.ds.resize_shape, fl)
-            ready = torch.cuda.Event()
-            ready.record(self.side)
-        return img, lab, ready
+    def on_slab(self, fields):
+        imgs, labs, shifts, flips = fields
+        if not self.ds.random:
+            shifts = flips = None
+        return (self.eng.segnet_train_input(imgs, self.ds.resize_shape, shifts, flips),
+                self.eng.segnet_train_label(labs, self.ds.resize_shape, flips))
 
     def from_host(self, batch):
-        torch = self.torch
-        return (torch.from_numpy(np.stack([b[0] for b in batch])).to(self.eng.device),
-                torch.from_numpy(np.stack([b[1] for b in batch])).to(self.eng.device), None)
-
-    def finish(self, out):
-        img, lab, ready = out
-        if ready is not None:
-            cur = self.torch.cuda.current_stream(self.eng.device)
-            cur.wait_event(ready)
-            img.record_stream(cur)
-            lab.record_stream(cur)
-        return img, lab
-
-    def close(self):
-        self.side.synchronize()
+        return tuple(self.torch.from_numpy(a).to(self.device) for a in _host_batch(batch)), None
 
 
-class WorkerPool(object):
-    """The spawned decode workers of one process (decode_worker.py), shared by its loaders: every user acquire()s it
-    and release()s it in its close(); the last release shuts it down.  spawn, not fork: the process may have
-    initialised the GPU.  The workers end with the process that made them (die_with_parent)."""
-
-    def __init__(self, n_procs):
-        import multiprocessing as mp
-        from concurrent.futures import ProcessPoolExecutor
-        self.n_procs = int(n_procs)
-        self.executor = ProcessPoolExecutor(max_workers=self.n_procs, mp_context=mp.get_context('spawn'),
-                                            initializer=decode_worker.die_with_parent, initargs=(os.getpid(),))
-        self.users = 0
-        self.pids = None
-
-    def acquire(self):
-        self.users += 1
-        return self
-
-    def warm(self):
-        """-> the workers' pids; the first call starts every worker and imports Pillow's PNG plugin in it"""
-        if self.pids is None:
-            self.pids = sorted(set(self.executor.map(decode_worker.warm, range(4 * self.n_procs))))
-        return self.pids
-
-    def release(self):
-        self.users -= 1
-        if self.users <= 0 and self.executor is not None:
-            self.executor.shutdown(wait=True, cancel_futures=True)
-            self.executor = None
-
-
-class Slabs(object):
-    """What a loader holds besides its batches: n_slabs shared-memory slabs of slab_bytes each (the caller counts one
-    spare, so a batch is never decoded into the slab whose upload was just enqueued), each registered with the stage
-    (DeviceStage: as pinned host memory, with one notice when that fails), and the worker pool, its own or the one
-    given.  Raises cli.ShmTooSmall where /dev/shm cannot hold the slabs, before anything else happens.  A
-    constructor that fails has closed what it had opened.  close() may be called any number of times."""
-
-    def __init__(self, what, slab_bytes, n_slabs, n_procs, stage, pool=None):
-        from multiprocessing import shared_memory
-        self.stage, self.slots, self.workers = stage, [], None
-        free = _shm_free()
-        if free is not None and free < n_slabs * slab_bytes + (16 << 20):
-            from .cli import ShmTooSmall
-            raise ShmTooSmall('/dev/shm has %d MB free, %s slabs need %d MB'
-                              % (free >> 20, what, (n_slabs * slab_bytes) >> 20))
-        try:
-            for _ in range(n_slabs):
-                shm = shared_memory.SharedMemory(create=True, size=slab_bytes)
-                slot = {'shm': shm, 'handle': None}
-                self.slots.append(slot)
-                slot['handle'] = stage.register(shm)
-            self.workers = (pool if pool is not None else WorkerPool(n_procs)).acquire()
-            self.pinned = all(s['handle']['pinned'] for s in self.slots)    # every slab is pinned host memory
-            self.worker_pids = self.workers.warm()
-        except BaseException:
-            self.close()
-            raise
-
-    def submit(self, fn, task):
-        return self.workers.executor.submit(fn, task)
-
-    def close(self, futures=()):
-        """futures: the owner's tasks still in flight; none of them writes into a slab after this returns"""
-        for f in futures:
-            f.cancel()
-        for f in futures:
-            if not f.cancelled():
-                try:
-                    f.exception()
-                except BaseException:
-                    pass
-        workers, self.workers = self.workers, None
-        if workers is not None:
-            workers.release()
-        slots, self.slots = self.slots, []
-        try:
-            self.stage.close()
-        finally:                                            # the slabs go whatever state the device is in
-            for s in slots:
-                if s['handle'] is not None:
-                    self.stage.unregister(s['handle'])
-                    s['handle'] = None
-                for release in (s['shm'].close, s['shm'].unlink):
-                    try:
-                        release()
-                    except Exception:
-                        pass
-
-
-class TrainLoader(object):
+class TrainLoader(Ring):
     """next() -> (images (B,3,h,w) float32, labels, (iterator state, numpy state) after that batch's draws): the plain
     loop's batches in its order.  dataset: a ZippedEstimatedCityscapesDataset; ids: the rank's example indices
     (train_ids); iterator: the ShuffledIterator the plain loop would call.  stage: a DeviceStage or a HostStage.
     pool: a WorkerPool to share (another loader's .workers); None: n_procs workers of its own.
-    Raises cli.ShmTooSmall where /dev/shm cannot hold the slabs, before anything is drawn.  close() stops the workers
-    and unregisters and unlinks the slabs; call it in a finally."""
+    Raises slabs.ShmTooSmall where /dev/shm cannot hold the slabs, before anything is drawn.  close() stops the
+    workers and unregisters and unlinks the slabs; call it in a finally."""
 
     def __init__(self, dataset, ids, iterator, n_procs, stage, depth=None, pool=None):
-        self.ds, self.ids, self.it, self.stage = dataset, np.asarray(ids), iterator, stage
-        self.B = int(iterator.batchsize)
-        self.depth = depth = int(depth or default_depth(n_procs, self.B))
+        self.ds, self.ids, self.it = dataset, np.asarray(ids), iterator
+        B = int(iterator.batchsize)
         self.ishape, self.lshape = _first_shapes(dataset)
         self.ldtype = np.dtype(np.float32 if dataset.use_soft_label else np.uint8)
-        align = lambda n: (n + 63) // 64 * 64
-        self.ibytes = int(np.prod(self.ishape))
-        self.lbytes = int(np.prod(self.lshape)) * self.ldtype.itemsize
-        self.lab_off = align(self.B * self.ibytes)
-        self.shift_off = align(self.lab_off + self.B * self.lbytes)
-        self.flip_off = self.shift_off + self.B * 24
-        slab = align(self.flip_off + self.B)
-        self.slots, self.free, self.pending = [], [], collections.deque()
-        self.pool = self.slabs = None
-        self.n_host_batches = 0            # batches that took the host path (another shape than the first example's)
-        self.slabs = Slabs('the training loader\'s', slab, depth + 1, n_procs, stage, pool)
-        self.slots, self.free = self.slabs.slots, list(self.slabs.slots)
-        self.workers, self.pool = self.slabs.workers, self.slabs.workers.executor
-        self.pinned, self.worker_pids = self.slabs.pinned, self.slabs.worker_pids
+        layout = Layout(B, [('frames', self.ishape, np.uint8), ('labels', self.lshape, self.ldtype),
+                            ('shifts', (3,), np.float64), ('flips', (), np.uint8)])
+        Ring.__init__(self, 'the training loader\'s', layout, depth or default_depth(n_procs, B), n_procs, stage, pool)
 
-    def _views(self, slot):
-        buf = np.frombuffer(slot['shm'].buf, dtype=np.uint8)
-        B = self.B
-        return (buf[:B * self.ibytes].reshape((B,) + self.ishape),
-                buf[self.lab_off:self.lab_off + B * self.lbytes].view(self.ldtype).reshape((B,) + self.lshape),
-                buf[self.shift_off:self.shift_off + B * 24].view(np.float64).reshape(B, 3),
-                buf[self.flip_off:self.flip_off + B])
-
-    def _submit(self):
+    def produce(self, name):
         """the draws of the next batch, in the plain loop's order, and its decode tasks"""
         ids = self.ids[self.it.next_indices()]
         shifts = flips = None
@@ -314,68 +126,40 @@ class TrainLoader(object):
                 shifts[j] = st.pca_lighting_shift(np.random.normal(0, 25.5, size=3))
                 flips[j] = np.random.rand() > 0.5
         state = ({k: np.array(v) for k, v in self.it.state().items()}, np.random.get_state())
-        slot = self.free.pop(0)
-        self.stage.wait(slot['handle'])
-        name = slot['shm'].name
-        tasks = [(decode_worker.decode_into, (name, j * self.ibytes, self.ishape,
+        at = self.layout.offset
+        tasks = [(decode_worker.decode_into, (name, at('frames', j), self.ishape,
                                               (self.ds.img_zip_fn, self.ds.img_fns[i]))) for j, i in enumerate(ids)]
-        tasks += [(decode_worker.label_into, (name, self.lab_off + j * self.lbytes, self.lshape,
+        tasks += [(decode_worker.label_into, (name, at('labels', j), self.lshape,
                                               (self.ds.label_zip_fn, self.ds.label_fns[i]))) for j, i in enumerate(ids)]
-        self.pending.append({'ids': ids, 'shifts': shifts, 'flips': flips, 'state': state, 'slot': slot, 'out': None,
-                             'futures': [self.slabs.submit(fn, t) for fn, t in tasks]})
+        return {'n': len(ids), 'ids': ids, 'shifts': shifts, 'flips': flips, 'state': state}, tasks
 
-    def _fill(self):
-        while self.free and len(self.pending) < self.depth:
-            self._submit()
-
-    def _stage(self, rec):
-        """wait for the batch's tasks, then the stage on its slab, or the host path for a batch with another shape"""
-        n = len(rec['ids'])
-        got = [f.result() for f in rec['futures']]
-        rec['futures'] = None
-        slot, rec['slot'] = rec['slot'], None
-        ok = all(tuple(g) == self.ishape for g in got[:n]) and all(
+    def fits(self, rec, got):
+        n = rec['n']
+        return all(tuple(g) == self.ishape for g in got[:n]) and all(
             tuple(g[0]) == self.lshape and (np.dtype(g[1]) == self.ldtype or
                                             (self.ldtype == np.uint8 and np.dtype(g[1]) == np.bool_)) for g in got[n:])
-        if ok:
-            views = self._views(slot)
+
+    def run(self, rec, handle, views):
+        if self.ds.random:
+            views[2][:rec['n']] = rec['shifts']
+            views[3][:rec['n']] = rec['flips']
+        return self.stage.run(handle, self.layout, views, rec['n'])
+
+    def host(self, rec):
+        """a batch with another shape: the dataset's host functions with the draws already made"""
+        batch = []
+        for j, i in enumerate(rec['ids']):
+            img, lab = self.ds.resized(*self.ds.decoded(i))
             if self.ds.random:
-                views[2][:n] = rec['shifts']
-                views[3][:n] = rec['flips']
-            rec['out'] = self.stage.run(slot['handle'], views, n, self.ds.random)
-            del views
-        else:
-            batch = []
-            for j, i in enumerate(rec['ids']):
-                img, lab = self.ds.resized(*self.ds.decoded(i))
-                if self.ds.random:
-                    batch.append(self.ds.augmented(img, lab, rec['shifts'][j], bool(rec['flips'][j])))
-                else:
-                    batch.append((np.ascontiguousarray(img, np.float32), np.ascontiguousarray(lab)))
-            rec['out'] = self.stage.from_host(batch)
-            self.n_host_batches += 1
-        self.free.append(slot)
+                batch.append(self.ds.augmented(img, lab, rec['shifts'][j], bool(rec['flips'][j])))
+            else:
+                batch.append((np.ascontiguousarray(img, np.float32), np.ascontiguousarray(lab)))
+        return self.stage.from_host(batch)
 
     def next(self):
-        self._fill()
-        rec = self.pending.popleft()
-        if rec['out'] is None:
-            self._stage(rec)
-        self._fill()
-        # the batch after this one, when its decodes are done already: its upload and kernels overlap the step
-        if self.pending and self.pending[0]['out'] is None and all(f.done() for f in self.pending[0]['futures']):
-            self._stage(self.pending[0])
-            self._fill()
+        rec = self.take()
         img, lab = self.stage.finish(rec['out'])
         return img, lab, rec['state']
-
-    def close(self):
-        futures = [f for rec in self.pending for f in (rec['futures'] or ())]
-        self.pending.clear()
-        self.free, self.slots, self.pool = [], [], None
-        slabs, self.slabs = self.slabs, None
-        if slabs is not None:
-            slabs.close(futures)
 
 
 # ------------------------------------------------------------------------------- labelling and validation
@@ -401,42 +185,24 @@ class LabelBatch(object):
         self.frames = self.label_ids = self.ids_host = None
 
 
-class HostLabelStage(HostStage):
+class HostLabelStage(HostSlabStage):
     """numpy in, numpy out, no GPU: copies of the slab's frames and label ids."""
 
-    def __init__(self, dataset=None):
-        HostStage.__init__(self, dataset)
-
-    def run(self, handle, views, n):
-        return views[0][:n].copy(), views[1][:n].copy()
+    def on_slab(self, fields):
+        return tuple(f.copy() for f in fields)
 
 
-class DeviceLabelStage(DeviceStage):
-    """One upload of the slab's frames and label ids on a side stream; finish() makes the current stream wait for it."""
+class DeviceLabelStage(DeviceSlabStage):
+    """The uploaded frames and label ids as they are."""
 
     def __init__(self, engine):
-        DeviceStage.__init__(self, None, engine)
+        DeviceSlabStage.__init__(self, engine.device, 'segnet_loader')
 
-    def run(self, handle, views, n):
-        torch = self.torch
-        imgs, ids = views[0][:n], views[1][:n]
-        base = views[0].__array_interface__['data'][0]
-        off = ids.__array_interface__['data'][0] - base
-        with torch.cuda.stream(self.side):
-            d = handle['t'][:off + ids.nbytes].to(self.eng.device, non_blocking=True)
-            handle['ev'] = torch.cuda.Event()
-            handle['ev'].record(self.side)
-        return (d[:imgs.nbytes].view(tuple(imgs.shape)), d[off:off + ids.nbytes].view(tuple(ids.shape)), handle['ev'])
-
-    def finish(self, out):
-        frames, ids, ready = out
-        cur = self.torch.cuda.current_stream(self.eng.device)
-        cur.wait_event(ready)
-        frames.record_stream(cur)
-        return frames, ids
+    def on_slab(self, fields):
+        return fields
 
 
-class LabelLoader(object):
+class LabelLoader(Ring):
     """The frames and labelIds images of a ZippedCityscapesRoadDataset's examples `indices`, in order, in batches of
     `batchsize` (the last may be short), decoded by workers a few batches ahead (default_depth) into slabs: what
     labels_from_segnet.save_labels and train_segnet.evaluate read with get_raw, one image after the other.
@@ -444,109 +210,51 @@ class LabelLoader(object):
     a frame or label of another shape than the first example's, or of another mode than RGB / L (for which np.asarray
     of the decoded image is not what get_raw's convert() gives), is marked host.  stage: a DeviceLabelStage or a
     HostLabelStage.  pool: a WorkerPool to share (a TrainLoader's .workers).  keep_ids: every batch also carries a
-    numpy copy of its label ids.  Raises cli.ShmTooSmall like TrainLoader; close() in a finally."""
+    numpy copy of its label ids.  Raises slabs.ShmTooSmall like TrainLoader; close() in a finally."""
 
     def __init__(self, dataset, indices, batchsize, n_procs, stage, depth=None, pool=None, keep_ids=False):
-        self.ds, self.indices, self.stage = dataset, [int(i) for i in indices], stage
-        self.B = max(int(batchsize), 1)
-        self.depth = depth = int(depth or default_depth(n_procs, self.B))
+        self.ds, self.indices, self.pos = dataset, [int(i) for i in indices], 0
         self.keep_ids = bool(keep_ids)
-        self.free, self.pending, self.pos = [], collections.deque(), 0
-        self.slabs = None
-        self.n_host_batches = 0
+        B = max(int(batchsize), 1)
         self.ishape, self.lshape = _first_png_shapes(dataset) if self.indices else ((1, 1, 3), (1, 1))
-        align = lambda n: (n + 63) // 64 * 64
-        self.ibytes, self.lbytes = int(np.prod(self.ishape)), int(np.prod(self.lshape))
-        self.lab_off = align(self.B * self.ibytes)
-        slab = align(self.lab_off + self.B * self.lbytes)
-        self.slabs = Slabs('the label loader\'s', slab, depth + 1, n_procs, stage, pool)
-        self.free = list(self.slabs.slots)
-        self.workers = self.slabs.workers
-        self.pinned, self.worker_pids = self.slabs.pinned, self.slabs.worker_pids
+        layout = Layout(B, [('frames', self.ishape, np.uint8), ('label_ids', self.lshape, np.uint8)])
+        Ring.__init__(self, 'the label loader\'s', layout, depth or default_depth(n_procs, B), n_procs, stage, pool)
 
-    def _views(self, slot):
-        buf = np.frombuffer(slot['shm'].buf, dtype=np.uint8)
-        B = self.B
-        return (buf[:B * self.ibytes].reshape((B,) + self.ishape),
-                buf[self.lab_off:self.lab_off + B * self.lbytes].reshape((B,) + self.lshape))
-
-    def _submit(self):
+    def produce(self, name):
         ids = self.indices[self.pos:self.pos + self.B]
+        if not ids:
+            return None
         self.pos += len(ids)
-        slot = self.free.pop(0)
-        self.stage.wait(slot['handle'])
-        name = slot['shm'].name
-        tasks = [(name, j * self.ibytes, self.ishape, 'RGB', (self.ds.img_zip_fn, self.ds.img_fns[i]))
+        at = self.layout.offset
+        tasks = [(name, at('frames', j), self.ishape, 'RGB', (self.ds.img_zip_fn, self.ds.img_fns[i]))
                  for j, i in enumerate(ids)]
-        tasks += [(name, self.lab_off + j * self.lbytes, self.lshape, 'L', (self.ds.label_zip_fn, self.ds.label_fns[i]))
+        tasks += [(name, at('label_ids', j), self.lshape, 'L', (self.ds.label_zip_fn, self.ds.label_fns[i]))
                   for j, i in enumerate(ids)]
-        self.pending.append({'batch': LabelBatch(ids), 'slot': slot, 'out': None,
-                             'futures': [self.slabs.submit(decode_worker.png_into, t) for t in tasks]})
+        return {'n': len(ids), 'batch': LabelBatch(ids)}, [(decode_worker.png_into, t) for t in tasks]
 
-    def _fill(self):
-        while self.free and len(self.pending) < self.depth and self.pos < len(self.indices):
-            self._submit()
+    def fits(self, rec, got):
+        want = [(self.ishape, 'RGB')] * rec['n'] + [(self.lshape, 'L')] * rec['n']
+        return all((tuple(g[0]), g[1]) == w for g, w in zip(got, want))
 
-    def _stage(self, rec):
-        batch = rec['batch']
-        n = len(batch.indices)
-        got = [f.result() for f in rec['futures']]
-        rec['futures'] = None
-        slot, rec['slot'] = rec['slot'], None
-        want = [(self.ishape, 'RGB')] * n + [(self.lshape, 'L')] * n
-        if all((tuple(g[0]), g[1]) == w for g, w in zip(got, want)):
-            views = self._views(slot)
-            if self.keep_ids:
-                batch.ids_host = views[1][:n].copy()
-            rec['out'] = self.stage.run(slot['handle'], views, n)
-            del views
-        else:
-            batch.host = True
-            rec['out'] = ()
-            self.n_host_batches += 1
-        self.free.append(slot)
+    def run(self, rec, handle, views):
+        if self.keep_ids:
+            rec['batch'].ids_host = views[1][:rec['n']].copy()
+        return self.stage.run(handle, self.layout, views, rec['n'])
 
-    def _drain(self):
-        """an abandoned pass: its tasks end before their slabs are used again"""
-        for rec in self.pending:
-            for f in rec['futures'] or ():
-                f.cancel()
-            for f in rec['futures'] or ():
-                if not f.cancelled():
-                    try:
-                        f.exception()
-                    except BaseException:
-                        pass
-            if rec['slot'] is not None:
-                self.free.append(rec['slot'])
-        self.pending.clear()
+    def host(self, rec):
+        rec['batch'].host = True
+        return ()
 
     def batches(self):
-        self._drain()
+        self.drain()
         self.pos = 0
         while True:
-            self._fill()
-            if not self.pending:
+            rec = self.take()
+            if rec is None:
                 return
-            rec = self.pending.popleft()
-            if rec['out'] is None:
-                self._stage(rec)
-            self._fill()
-            # the batch after this one, when its decodes are done already: its upload overlaps this batch's work
-            if self.pending and self.pending[0]['out'] is None and all(f.done() for f in self.pending[0]['futures']):
-                self._stage(self.pending[0])
-                self._fill()
             batch = rec['batch']
             if not batch.host:
                 batch.frames, batch.label_ids = self.stage.finish(rec['out'])
             yield batch
 
     __iter__ = batches
-
-    def close(self):
-        futures = [f for rec in self.pending for f in (rec['futures'] or ())]
-        self.pending.clear()
-        self.free = []
-        slabs, self.slabs = self.slabs, None
-        if slabs is not None:
-            slabs.close(futures)

@@ -23,6 +23,7 @@ import segnet_train_synth as syn  # noqa: E402
 segnet = importlib.import_module('superpixel-align_amd.segnet')
 st = importlib.import_module('superpixel-align_amd.segnet_train')
 sl = importlib.import_module('superpixel-align_amd.segnet_loader')
+slabs = importlib.import_module('superpixel-align_amd.slabs')
 dw = importlib.import_module('superpixel-align_amd.decode_worker')
 cli = importlib.import_module('superpixel-align_amd.cli')
 lfs = importlib.import_module('labels_from_segnet')
@@ -126,7 +127,7 @@ def test_close_twice_and_after_a_failed_constructor(data, monkeypatch):
     with pytest.raises(RuntimeError, match='no second slab'):
         sl.LabelLoader(data['ds'], range(6), 2, 2, Failing())
     assert syn.shm_names() == before
-    monkeypatch.setattr(sl, '_shm_free', lambda: 1 << 20)
+    monkeypatch.setattr(slabs, '_shm_free', lambda: 1 << 20)
     with pytest.raises(cli.ShmTooSmall, match='label loader'):
         sl.LabelLoader(data['ds'], range(6), 2, 2, sl.HostLabelStage())
     assert syn.shm_names() == before
@@ -280,7 +281,7 @@ def test_small_shm_takes_the_plain_loop(data, tmp_path, monkeypatch, capsys):
     monkeypatch.setattr(torch.cuda, 'set_device', lambda d: None)
     monkeypatch.setattr(segnet.SegNetBasic, 'from_snapshot', classmethod(lambda cls, *a, **kw: model))
     monkeypatch.setattr(sl, 'DeviceLabelStage', lambda engine: sl.HostLabelStage())
-    monkeypatch.setattr(sl, '_shm_free', lambda: 1 << 20)
+    monkeypatch.setattr(slabs, '_shm_free', lambda: 1 << 20)
     param_dir = tmp_path / 'run'
     param_dir.mkdir()
     with open(str(param_dir / 'args.txt'), 'w') as f:

@@ -25,6 +25,7 @@ import segnet_train_synth as syn  # noqa: E402
 
 st = importlib.import_module('superpixel-align_amd.segnet_train')
 sl = importlib.import_module('superpixel-align_amd.segnet_loader')
+slabs = importlib.import_module('superpixel-align_amd.slabs')
 dw = importlib.import_module('superpixel-align_amd.decode_worker')
 cli = importlib.import_module('superpixel-align_amd.cli')
 train_segnet = importlib.import_module('train_segnet')
@@ -208,7 +209,7 @@ def test_off_size_frame_takes_the_host_path(tmp_path):
 def test_small_shm_is_refused_before_any_draw(tmp_path, monkeypatch):
     z = syn.write(str(tmp_path / 'data'), 4, 1, 32, 64)
     ds = st.ZippedEstimatedCityscapesDataset(z[0], z[1], (32, 64), True, False)
-    monkeypatch.setattr(sl, '_shm_free', lambda: 1 << 20)
+    monkeypatch.setattr(slabs, '_shm_free', lambda: 1 << 20)
     np.random.seed(0)
     it = st.ShuffledIterator(4, 2)
     state = np.random.get_state()
@@ -228,7 +229,7 @@ def test_driver_says_so_once_and_goes_on_without_the_loader(tmp_path, monkeypatc
     it = st.ShuffledIterator(4, 2)
     state = np.random.get_state()
     with monkeypatch.context() as m:
-        m.setattr(sl, '_shm_free', lambda: 1 << 20)
+        m.setattr(slabs, '_shm_free', lambda: 1 << 20)
         assert train_segnet.open_loader(2, ds, np.arange(4), it, sl.HostStage(ds)) is None
     out = capsys.readouterr().out
     assert out.count('\n') == 1 and '--loader_procs: /dev/shm has 1 MB free' in out

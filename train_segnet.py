@@ -267,24 +267,16 @@ def open_loader(n_procs, train, train_ids, it, stage):
     """-> the run's segnet_loader.TrainLoader on n_procs workers, or None where /dev/shm cannot hold its slabs: the
     run says so once and prepares its batches itself (nothing has been drawn, so the bits are the same)."""
     sl = importlib.import_module('superpixel-align_amd.segnet_loader')
-    cli = importlib.import_module('superpixel-align_amd.cli')
-    try:
-        return sl.TrainLoader(train, train_ids, it, n_procs, stage)
-    except cli.ShmTooSmall as e:
-        print('--loader_procs: %s; the batches are prepared on the host' % e, flush=True)
-        return None
+    return sl.open_or_none(lambda: sl.TrainLoader(train, train_ids, it, n_procs, stage),
+                           '--loader_procs: %s; the batches are prepared on the host')
 
 
 def open_label_loader(n_procs, valid, valid_ids, batchsize, stage, pool=None):
     """-> the run's segnet_loader.LabelLoader over the rank's validation indices (on the training loader's workers
     where `pool` is given), or None where /dev/shm cannot hold its slabs: one line, and validation decodes on the host"""
     sl = importlib.import_module('superpixel-align_amd.segnet_loader')
-    cli = importlib.import_module('superpixel-align_amd.cli')
-    try:
-        return sl.LabelLoader(valid, valid_ids, batchsize, n_procs, stage, pool=pool)
-    except cli.ShmTooSmall as e:
-        print('--loader_procs: %s; the validation images are decoded on the host' % e, flush=True)
-        return None
+    return sl.open_or_none(lambda: sl.LabelLoader(valid, valid_ids, batchsize, n_procs, stage, pool=pool),
+                           '--loader_procs: %s; the validation images are decoded on the host')
 
 
 def main(argv=None):
