@@ -644,6 +644,42 @@ int spa_segnet_train_wgrad_f16x3(spa_ctx *ctx, const float *dy, const float *x, 
                                  int32_t B, int32_t H, int32_t W, int32_t Cin, const float *mean_host,
                                  const float *std_host, float *dw, void *stream);
 
+/* ---- SegNet-Basic training, between the convolutions (train_segnet.py --fused_bn; csrc/spa_segnet_train_bn.hip) --
+ * BatchNorm with ReLU and 2x2 max pooling, its backward, and the 64 -> 2 classifier.  Maps are contiguous (B,H,W,64)
+ * float32, channels-last; index maps are uint8 ky*2+kx, the first maximum; mean, rstd, gamma, beta are (64) float32 on
+ * the device.  Any B >= 1 and any even H, W >= 2 (the FULL resolution of the layer); every offset is 64-bit and no size
+ * limit remains.  Maps and per-channel vectors must be 16-byte aligned, index maps 4-byte, the score maps and float64
+ * sums 8-byte.  A refused call (SPA_ERR_ARG) launches nothing.  No atomics: the reductions add float32 runs of at most
+ * 32 pixels per lane into doubles, the lanes and workgroups in a fixed order that depends on (B,H,W) alone, so the same
+ * call gives the same bits on every run and device.  Workspaces belong to the context; no host synchronisation. */
+/* o = (y - mean) * (rstd * gamma) + beta, each operation rounded to float32 on its own.  idx NULL (decoder form): out
+ * (B,H,W,64) = o.  idx (B,H/2,W/2,64) (encoder form): out (B,H/2,W/2,64) = the 2x2 maximum of relu(o) and idx the
+ * position of its first maximum; a window whose four o are all <= 0 gives 0 and index 0. */
+int spa_segnet_train_bn_forward(spa_ctx *ctx, const float *y, const float *mean, const float *rstd, const float *gamma,
+                                const float *beta, int32_t B, int32_t H, int32_t W, float *out, uint8_t *idx,
+                                void *stream);
+/* sums (2,64) float64 = (sum g, sum g * xhat) over (B,H,W), xhat = (y - mean) * rstd.  idx, p NULL (decoder form): g
+ * (B,H,W,64) the gradient at o.  idx, p (B,H/2,W/2,64) (encoder form, both or neither): g (B,H/2,W/2,64) the gradient at
+ * the pooled map and p the pooled map the forward stored; the full-resolution gradient is g at the position idx
+ * selects where p > 0 (the ReLU mask) and zero elsewhere, so only the selected elements of y are read. */
+int spa_segnet_train_bn_backward_sums(spa_ctx *ctx, const float *g, const uint8_t *idx, const float *p, const float *y,
+                                      const float *mean, const float *rstd, int32_t B, int32_t H, int32_t W,
+                                      double *sums, void *stream);
+/* dy (B,H,W,64) = (gamma * rstd / m) * (m * g - S0 - xhat * S1), computed as gamma * rstd * ((g - S0 / m) - xhat *
+ * (S1 / m)) with the two quotients formed in float64 and rounded once.  sums (2,64) float64 on the device = (S0, S1):
+ * the sums above, or in a data-parallel step their total over the ranks with m the pixels of all ranks (m >= 1).  g,
+ * idx, p take the two forms above. */
+int spa_segnet_train_bn_backward_dy(spa_ctx *ctx, const float *g, const uint8_t *idx, const float *p, const float *y,
+                                    const float *mean, const float *rstd, const float *gamma, const double *sums,
+                                    double m, int32_t B, int32_t H, int32_t W, float *dy, void *stream);
+/* score (B,H,W,2) float32 = h * wc^T + bc: h (B,H,W,64), wc (2,64), bc (2). */
+int spa_segnet_train_classifier_forward(spa_ctx *ctx, const float *h, const float *wc, const float *bc, int32_t B,
+                                        int32_t H, int32_t W, float *score, void *stream);
+/* dh (B,H,W,64) = dscore * wc; dwc (2,64) = sum over (B,H,W) of dscore[k] * h[c]; db (2) = sum of dscore[k]: float64
+ * sums formed as above, rounded once.  dscore (B,H,W,2). */
+int spa_segnet_train_classifier_backward(spa_ctx *ctx, const float *dscore, const float *h, const float *wc, int32_t B,
+                                         int32_t H, int32_t W, float *dh, float *dwc, float *db, void *stream);
+
 /* save_info() scoring (:398-405): per image confusion of road (B,npix) uint8 against
    gt (B,npix) int32 in {-1 ignore, 0, 1} -> out (B,4) int64 {TN, FP, FN, TP}.             */
 int spa_confusion(spa_ctx *ctx, const uint8_t *road, const int32_t *gt, int32_t B,

@@ -159,6 +159,14 @@ PROTOTYPES = {
     'spa_segnet_train_dgrad_f16x3': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
     'spa_segnet_train_wgrad_f16x3': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p,
                                                     c_p, c_p]),
+    'spa_segnet_train_bn_forward': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
+    'spa_segnet_train_bn_backward_sums': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p,
+                                                         c_p]),
+    'spa_segnet_train_bn_backward_dy': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_i32, c_i32,
+                                                       c_i32, c_p, c_p]),
+    'spa_segnet_train_classifier_forward': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
+    'spa_segnet_train_classifier_backward': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p,
+                                                            c_p]),
 }
 
 

@@ -91,6 +91,7 @@ enum {
     WS_SEGNET_WBF16,   // SegNet bf16 training forward / dgrad and bf16 inference: the weights rounded to bf16
     WS_SEGNET_WF16X3,  // SegNet split-plane training forward / dgrad and inference: the weights as two scaled f16 planes
     WS_SEGNET_AMAX,    // SegNet split-plane training and inference: per-workgroup maxima and the operands' scale exponents
+    WS_SEGNET_BNRED,   // SegNet fused BatchNorm / classifier backward: per-workgroup float64 partial sums
     WS_COUNT
 };
 

@@ -1109,6 +1109,116 @@ class Engine(object):
         check(fn(self._ctx, _ptr(dy), _ptr(x), _ptr(idx), layout, B, H, W, cin, m, s, _ptr(dw), self._s()))
         return dw
 
+    # ---- SegNet-Basic training between the convolutions (SegNetTrainer(fused_bn=True); csrc/spa_segnet_train_bn.hip).
+    # y is the layer's (B,H,W,64) convolution output; mean, rstd, gamma, beta are (64) float32.  The encoder forms take
+    # the (B,H/2,W/2,64) pooled map p, its index map idx and the gradient g at the pooled map, the decoder forms the
+    # full-resolution gradient g alone.
+    @staticmethod
+    def _bn_map(y, what='y'):
+        _req(y, torch.float32, what)
+        if y.dim() != 4 or y.shape[3] != 64 or y.shape[1] % 2 or y.shape[2] % 2 or y.numel() == 0:
+            raise SpalignError('segnet_train_bn: %s must be (B,H,W,64) with even H, W, got %s' % (what, tuple(y.shape)))
+        return tuple(y.shape)
+
+    @staticmethod
+    def _bn_vectors(**vectors):
+        for name, v in vectors.items():
+            _req(v, torch.float32, name)
+            if tuple(v.shape) != (64,):
+                raise SpalignError('segnet_train_bn: %s must be (64,), got %s' % (name, tuple(v.shape)))
+
+    @staticmethod
+    def _bn_out(out, shape, dtype, device, what='out'):
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=device)
+        _req(out, dtype, what)
+        if tuple(out.shape) != tuple(shape):
+            raise SpalignError('segnet_train_bn: %s must be %s, got %s' % (what, tuple(shape), tuple(out.shape)))
+        return out
+
+    def _bn_gradient(self, g, idx, p, y):
+        """checks the gradient form (g, idx, p) of a backward call against y -> (B, H, W)"""
+        B, H, W, _ = self._bn_map(y)
+        _req(g, torch.float32, 'g')
+        if (idx is None) != (p is None):
+            raise SpalignError('segnet_train_bn: idx and p come together (the encoder form) or not at all')
+        shape = (B, H, W, 64) if idx is None else (B, H // 2, W // 2, 64)
+        if tuple(g.shape) != shape:
+            raise SpalignError('segnet_train_bn: g must be %s, got %s' % (shape, tuple(g.shape)))
+        if idx is not None:
+            _req(idx, torch.uint8, 'idx')
+            _req(p, torch.float32, 'p')
+            if tuple(idx.shape) != shape or tuple(p.shape) != shape:
+                raise SpalignError('segnet_train_bn: idx and p must be %s, got %s and %s'
+                                   % (shape, tuple(idx.shape), tuple(p.shape)))
+        return B, H, W
+
+    def segnet_train_bn_forward(self, y, mean, rstd, gamma, beta, pool=False, out=None, out_idx=None):
+        """o = (y - mean) * (rstd * gamma) + beta.  pool False (decoder): -> o (B,H,W,64).  pool True (encoder): ->
+        (the 2x2 maximum of relu(o) (B,H/2,W/2,64), the uint8 index ky*2+kx of its first maximum)."""
+        B, H, W, _ = self._bn_map(y)
+        self._bn_vectors(mean=mean, rstd=rstd, gamma=gamma, beta=beta)
+        if not pool:
+            if out_idx is not None:
+                raise SpalignError('segnet_train_bn_forward: out_idx belongs to pool=True')
+            o = self._bn_out(out, (B, H, W, 64), torch.float32, y.device)
+            idx = None
+        else:
+            o = self._bn_out(out, (B, H // 2, W // 2, 64), torch.float32, y.device)
+            idx = self._bn_out(out_idx, (B, H // 2, W // 2, 64), torch.uint8, y.device, 'out_idx')
+        check(self._lib.spa_segnet_train_bn_forward(self._ctx, _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
+                                                    B, H, W, _ptr(o), _ptr(idx), self._s()))
+        return (o, idx) if pool else o
+
+    def segnet_train_bn_backward_sums(self, g, y, mean, rstd, idx=None, p=None, out=None):
+        """-> (2,64) float64: (sum g, sum g * xhat) over (B,H,W), xhat = (y - mean) * rstd, g in either form."""
+        B, H, W = self._bn_gradient(g, idx, p, y)
+        self._bn_vectors(mean=mean, rstd=rstd)
+        s = self._bn_out(out, (2, 64), torch.float64, y.device)
+        check(self._lib.spa_segnet_train_bn_backward_sums(self._ctx, _ptr(g), _ptr(idx), _ptr(p), _ptr(y), _ptr(mean),
+                                                          _ptr(rstd), B, H, W, _ptr(s), self._s()))
+        return s
+
+    def segnet_train_bn_backward_dy(self, g, y, mean, rstd, gamma, sums, m, idx=None, p=None, out=None):
+        """-> dy (B,H,W,64) = (gamma * rstd / m) * (m * g - sums[0] - xhat * sums[1]); sums (2,64) float64 on the
+        device (segnet_train_bn_backward_sums, summed over the ranks in a data-parallel step), m the pixel count."""
+        B, H, W = self._bn_gradient(g, idx, p, y)
+        self._bn_vectors(mean=mean, rstd=rstd, gamma=gamma)
+        _req(sums, torch.float64, 'sums')
+        if tuple(sums.shape) != (2, 64) or not float(m) >= 1.0:
+            raise SpalignError('segnet_train_bn_backward_dy: sums must be (2,64) and m >= 1')
+        dy = self._bn_out(out, (B, H, W, 64), torch.float32, y.device)
+        check(self._lib.spa_segnet_train_bn_backward_dy(self._ctx, _ptr(g), _ptr(idx), _ptr(p), _ptr(y), _ptr(mean),
+                                                        _ptr(rstd), _ptr(gamma), _ptr(sums), float(m), B, H, W,
+                                                        _ptr(dy), self._s()))
+        return dy
+
+    def segnet_train_classifier_forward(self, h, wc, bc, out=None):
+        """score (B,H,W,2) = h (B,H,W,64) * wc (2,64)^T + bc (2)."""
+        B, H, W, _ = self._bn_map(h, 'h')
+        _req(wc, torch.float32, 'wc')
+        _req(bc, torch.float32, 'bc')
+        if tuple(wc.shape) != (2, 64) or tuple(bc.shape) != (2,):
+            raise SpalignError('segnet_train_classifier_forward: wc must be (2,64) and bc (2,)')
+        score = self._bn_out(out, (B, H, W, 2), torch.float32, h.device)
+        check(self._lib.spa_segnet_train_classifier_forward(self._ctx, _ptr(h), _ptr(wc), _ptr(bc), B, H, W,
+                                                            _ptr(score), self._s()))
+        return score
+
+    def segnet_train_classifier_backward(self, dscore, h, wc, out=None, out_dw=None, out_db=None):
+        """-> (dh (B,H,W,64) = dscore * wc, dwc (2,64), db (2)) for dscore (B,H,W,2)."""
+        B, H, W, _ = self._bn_map(h, 'h')
+        _req(dscore, torch.float32, 'dscore')
+        _req(wc, torch.float32, 'wc')
+        if tuple(dscore.shape) != (B, H, W, 2) or tuple(wc.shape) != (2, 64):
+            raise SpalignError('segnet_train_classifier_backward: dscore must be %s and wc (2,64)' % ((B, H, W, 2),))
+        dh = self._bn_out(out, (B, H, W, 64), torch.float32, h.device)
+        dw = self._bn_out(out_dw, (2, 64), torch.float32, h.device, 'out_dw')
+        db = self._bn_out(out_db, (2,), torch.float32, h.device, 'out_db')
+        check(self._lib.spa_segnet_train_classifier_backward(self._ctx, _ptr(dscore), _ptr(h), _ptr(wc), B, H, W,
+                                                             _ptr(dh), _ptr(dw), _ptr(db), self._s()))
+        return dh, dw, db
+
     def confusion(self, road, gt):
         """road (B,H,W) u8, gt (B,H,W) i32 in {-1,0,1} -> (B,4) i64 {TN, FP, FN, TP}."""
         road = _req(road, torch.uint8, 'road')

@@ -25,6 +25,13 @@ step at float32 accuracy on the f16 matrix cores (csrc/spa_segnet_train_f16x3.hi
 power of two and carried as two half-precision planes, three products per float32 product, float32 accumulation.
 Everything else is the float32 path unchanged; its float64 restatement is `reference_loss` with unrounded operands.
 
+fused_bn (SegNetTrainer(..., fused_bn=True), train_segnet.py --fused_bn; with any of the three convolution families)
+runs what lies between the convolutions on the kernels of csrc/spa_segnet_train_bn.hip instead of torch ops: an encoder
+layer's BatchNorm + ReLU + pooling in one pass that stores the pooled map and its index map, a decoder layer's
+BatchNorm, their backward (the two per-channel sums in float64, then dy) and the classifier with its backward.  The
+batch statistics, the mean / var / rstd arithmetic, bn_update, the losses and the optimizers are the code below
+unchanged; `reference_loss` is its float64 restatement too.
+
 Data parallelism (train_segnet.py --data_parallel, SegNetTrainer.set_group(RankGroup())): one rank per GPU under
 torchrun, BatchNorm over the union of the ranks' batches and the mean of the ranks' gradients; see RankGroup.
 """
@@ -352,25 +359,100 @@ def _functions():
     return Conv7, BatchNorm
 
 
+def _fused_functions():
+    """The layers between the convolutions on the kernels of csrc/spa_segnet_train_bn.hip (fused_bn=True).  Against the
+    autograd graph of BatchNorm / relu / pool_argmax_nhwc / matmul, an encoder layer saves y, the pooled map and its
+    uint8 index map (not the normalised map, the ReLU output and the windowed copy), a decoder layer y alone."""
+    torch = _torch()
+
+    def bn_backward(ctx, g, idx, p):
+        y, gamma, mean, rstd = ctx.saved_tensors[:4]
+        eng = ctx.eng
+        m = y.numel() / y.shape[-1]
+        g = g.contiguous()
+        sums = eng.segnet_train_bn_backward_sums(g, y, mean, rstd, idx, p)
+        total = sums
+        if ctx.group is not None:           # as BatchNorm: dy from every rank's sums, gamma and beta from this rank's
+            m *= ctx.group.size
+            total = ctx.group.sum_in_rank_order(sums)
+        dy = eng.segnet_train_bn_backward_dy(g, y, mean, rstd, gamma, total, m, idx, p)
+        return dy, sums[1].float(), sums[0].float(), None, None, None, None
+
+    class EncoderBN(torch.autograd.Function):
+        """(max over 2x2 of relu(bn(y)), the index of its first maximum) for given batch statistics"""
+
+        @staticmethod
+        def forward(ctx, y, gamma, beta, mean, rstd, eng, group=None):
+            p, idx = eng.segnet_train_bn_forward(y, mean, rstd, gamma.detach(), beta.detach(), pool=True)
+            ctx.save_for_backward(y, gamma, mean, rstd, idx, p)
+            ctx.eng, ctx.group = eng, group
+            ctx.mark_non_differentiable(idx)
+            return p, idx
+
+        @staticmethod
+        def backward(ctx, gp, _gidx):
+            idx, p = ctx.saved_tensors[4:]
+            return bn_backward(ctx, gp, idx, p)
+
+    class DecoderBN(torch.autograd.Function):
+        """bn(y) for given batch statistics"""
+
+        @staticmethod
+        def forward(ctx, y, gamma, beta, mean, rstd, eng, group=None):
+            ctx.save_for_backward(y, gamma, mean, rstd)
+            ctx.eng, ctx.group = eng, group
+            return eng.segnet_train_bn_forward(y, mean, rstd, gamma.detach(), beta.detach())
+
+        @staticmethod
+        def backward(ctx, g):
+            return bn_backward(ctx, g, None, None)
+
+    class Classifier(torch.autograd.Function):
+        """score (B,H,W,2) = h wc^T + bc for the (2,64,1,1) classifier weight"""
+
+        @staticmethod
+        def forward(ctx, h, wc, bc, eng):
+            w2 = wc.detach().reshape(2, 64).contiguous()
+            ctx.save_for_backward(h, w2)
+            ctx.eng = eng
+            return eng.segnet_train_classifier_forward(h, w2, bc.detach())
+
+        @staticmethod
+        def backward(ctx, g):
+            h, w2 = ctx.saved_tensors
+            dh, dw, db = ctx.eng.segnet_train_classifier_backward(g.contiguous(), h, w2)
+            return dh, dw.view(2, 64, 1, 1), db, None
+
+    return EncoderBN, DecoderBN, Classifier
+
+
 _FN = []
+_FUSED_FN = []
 
 
 class SegNetTrainer(object):
     """Parameters, running statistics and the optimizer of one SegNetBasic on one GPU.  P: float32 tensors keyed as
     the snapshot (conv1/W, conv1_bn/gamma, ..., conv_classifier/b), S: the running statistics.  dtype 'fp32' or
     'bf16': the operands of the 7x7 passes (see the module docstring); P, S and the optimizer are float32 in both.
-    split_planes (float32 only): the 7x7 passes at float32 accuracy on the f16 matrix cores."""
+    split_planes (float32 only): the 7x7 passes at float32 accuracy on the f16 matrix cores.  fused_bn: BatchNorm, ReLU,
+    pooling and the classifier, forward and backward, on the kernels of csrc/spa_segnet_train_bn.hip instead of torch
+    ops; it combines with every convolution family and with a RankGroup, and holds no state."""
 
-    def __init__(self, params, optimizer, lossfun, engine=None, device=None, dtype='fp32', split_planes=False):
+    def __init__(self, params, optimizer, lossfun, engine=None, device=None, dtype='fp32', split_planes=False,
+                 fused_bn=False):
         if dtype not in DTYPES:
             raise ValueError('SegNetTrainer: dtype must be one of %s, got %r' % (DTYPES, dtype))
         if split_planes and dtype != 'fp32':
             raise ValueError("SegNetTrainer: split_planes=True runs the float32 step on split planes; it does not "
                              "combine with dtype=%r" % (dtype,))
+        if not isinstance(fused_bn, bool):
+            raise ValueError('SegNetTrainer: fused_bn must be True or False, got %r' % (fused_bn,))
         torch = _torch()
         from .engine import Engine
         if not _FN:
             _FN.extend(_functions())
+        if fused_bn and not _FUSED_FN:
+            _FUSED_FN.extend(_fused_functions())
         self.eng = engine or Engine(device)
         dev = self.eng.device
         self.P = {k: torch.as_tensor(np.asarray(params[k]), dtype=torch.float32).to(dev).contiguous() for k in PARAM_KEYS}
@@ -381,6 +463,7 @@ class SegNetTrainer(object):
         self.dtype = dtype
         self.split_planes = bool(split_planes)
         self.family = '_f16x3' if self.split_planes else ('_bf16' if dtype == 'bf16' else '')
+        self.fused_bn = fused_bn
         self.group = None           # a RankGroup: data-parallel steps (set_group)
 
     def set_group(self, group):
@@ -403,8 +486,11 @@ class SegNetTrainer(object):
         h, pools = img.contiguous(), []
 
         group = self.group
+        fused = self.fused_bn
+        if fused:
+            EncoderBN, DecoderBN, Classifier = _FUSED_FN
 
-        def bn(name, y, stats):
+        def bn(name, y, stats, layer=None):
             m = float(y.shape[0] * y.shape[1] * y.shape[2])
             if group is not None:
                 stats = group.sum_in_rank_order(stats)
@@ -415,20 +501,28 @@ class SegNetTrainer(object):
             with torch.no_grad():
                 bn_update(self.S[name + '_bn/avg_mean'], self.S[name + '_bn/avg_var'], mean.float(), var.float(), m)
             self.N[name] += 1
+            if layer is not None:
+                return layer.apply(y, P[name + '_bn/gamma'], P[name + '_bn/beta'], mean.float(), rstd, self.eng, group)
             return BatchNorm.apply(y, P[name + '_bn/gamma'], P[name + '_bn/beta'], mean.float(), rstd, group)
 
         for name in ENCODERS:
             y, stats = Conv7.apply(h, pack_w(P[name + '/W']), None, self.eng, self.family)
-            a = torch.relu(bn(name, y, stats))
-            h, idx = pool_argmax_nhwc(a)
-            h = h.contiguous()
+            if fused:
+                h, idx = bn(name, y, stats, EncoderBN)
+            else:
+                a = torch.relu(bn(name, y, stats))
+                h, idx = pool_argmax_nhwc(a)
+                h = h.contiguous()
             pools.append(idx)
         if trace is not None:
             trace.extend(pools)
         for name, idx in zip(DECODERS, pools[::-1]):
             y, stats = Conv7.apply(h, pack_w(P[name + '/W']), idx, self.eng, self.family)
-            h = bn(name, y, stats)
-        score = torch.matmul(h, P['conv_classifier/W'].view(2, 64).t()) + P['conv_classifier/b']
+            h = bn(name, y, stats, DecoderBN if fused else None)
+        if fused:
+            score = Classifier.apply(h, P['conv_classifier/W'], P['conv_classifier/b'], self.eng)
+        else:
+            score = torch.matmul(h, P['conv_classifier/W'].view(2, 64).t()) + P['conv_classifier/b']
         return self.lossfun(score.permute(0, 3, 1, 2), t)
 
     def step(self, img, t, trace=None):

@@ -27,6 +27,13 @@ per float32 product).  Everything else is the float32 path.  It does not combine
 args.txt records "split_planes": true and every snapshot an extensions/split_planes entry; --resume follows the
 command-line flag (the state is float32 either way), and labels_from_segnet.py reads the snapshots unchanged.
 
+--fused_bn (also parsed in front of the reference flags): run what lies between the 7x7 convolutions -- BatchNorm, ReLU,
+2x2 pooling with its index maps, the classifier, forward and backward -- on the kernels of
+csrc/spa_segnet_train_bn.hip instead of torch ops (SegNetTrainer(fused_bn=True)).  It combines with --dtype bf16,
+--split_planes, --data_parallel, --loader_procs and --resume.  The losses and the optimizers stay in torch.  The mode
+holds no state: a snapshot gets no new entry, --resume follows the command line, and a resumed fused run continues a
+fused run bit for bit.  args.txt records "fused_bn": true only when the flag is given.  Validation is untouched.
+
 --data_parallel (also parsed in front of the reference flags): run as one rank of a torchrun launch (RANK, WORLD_SIZE,
 LOCAL_RANK; dist.init binds the rank's GPU), what the reference does under mpiexec with ChainerMN.  A step computes
 the gradient of the mean of the ranks' losses with BatchNorm over all ranks' batches (segnet_train.RankGroup).  Rank
@@ -122,8 +129,8 @@ def get_dtype_args(argv=None):
 
 def get_pre_args(argv=None):
     """-> (namespace of this implementation's flags, the remaining arguments for get_args): --dtype (get_dtype_args),
-    --split_planes, --val_split_planes, --data_parallel and --loader_procs, read by one pre-parser in front of the
-    reference flag set of get_parser."""
+    --split_planes, --val_split_planes, --fused_bn, --data_parallel and --loader_procs, read by one pre-parser in front
+    of the reference flag set of get_parser."""
     argv = list(sys.argv[1:] if argv is None else argv)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'],
@@ -132,6 +139,8 @@ def get_pre_args(argv=None):
                      help='float32 step with its 7x7 passes at float32 accuracy on the f16 matrix cores')
     pre.add_argument('--val_split_planes', action='store_true', default=False,
                      help='validation passes at float32 accuracy on the f16 matrix cores (SegNetBasic split_planes)')
+    pre.add_argument('--fused_bn', action='store_true', default=False,
+                     help='BatchNorm, ReLU, pooling and the classifier of the step on fused kernels instead of torch ops')
     pre.add_argument('--data_parallel', action='store_true', default=False,
                      help='run as one rank of a torchrun launch (RANK / WORLD_SIZE / LOCAL_RANK)')
     pre.add_argument('--loader_procs', type=int, default=0,
@@ -148,7 +157,7 @@ def check_split_planes(pre):
 
 def run_args(argv=None):
     """-> (the pre-parser's namespace, the run's arguments as args.txt records them, before a data-parallel run adds
-    its world size): the reference flags plus dtype, and split_planes / val_split_planes / data_parallel /
+    its world size): the reference flags plus dtype, and split_planes / val_split_planes / fused_bn / data_parallel /
     loader_procs only where they are given."""
     pre, argv = get_pre_args(argv)
     check_split_planes(pre)
@@ -158,6 +167,8 @@ def run_args(argv=None):
         args.split_planes = True                   # args.txt records it; a default run's args.txt is unchanged
     if pre.val_split_planes:
         args.val_split_planes = True               # likewise: recorded only when given
+    if pre.fused_bn:
+        args.fused_bn = True                       # likewise
     if pre.data_parallel:
         args.data_parallel = True                  # args.txt records it with the world size; one-process runs unchanged
     if pre.loader_procs < 0:
@@ -331,7 +342,7 @@ def main(argv=None):
         opt = st.MomentumSGD(args.lr, weight_decay=args.weight_decay)
     device = torch.cuda.current_device()
     trainer = st.SegNetTrainer(st.init_params(0), opt, lossfun, engine=eng, device=device, dtype=args.dtype,
-                               split_planes=pre.split_planes)
+                               split_planes=pre.split_planes, fused_bn=pre.fused_bn)
     it = st.ShuffledIterator(len(train_ids), args.batchsize)
 
     result_dir = None
@@ -353,7 +364,7 @@ def main(argv=None):
         if st.snapshot_split_planes(args.resume) != pre.split_planes and rank == 0:
             print('resuming a %s snapshot %s --split_planes' % (snap_dtype, 'with' if pre.split_planes else 'without'))
         trainer = st.SegNetTrainer(params, opt, lossfun, engine=trainer.eng, dtype=args.dtype,
-                                   split_planes=pre.split_planes)
+                                   split_planes=pre.split_planes, fused_bn=pre.fused_bn)
         opt.t = t
         if args.optimizer == 'MomentumSGD':
             opt.lr = lr

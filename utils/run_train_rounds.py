@@ -32,7 +32,9 @@ only), --label_dtype (the labelling passes' convolution precision, labels_from_s
 whatever --dtype is), --split_planes (the training rounds' train_segnet.py --split_planes: float32 steps with their
 convolution passes on split f16 planes; passed to the training children only when given), --label_split_planes (the
 labelling passes' labels_from_segnet.py --split_planes: float32-accurate inference on the f16 matrix cores;
-independent of --split_planes and --dtype, refused with --label_dtype bf16), --loader_procs (the training rounds'
+independent of --split_planes and --dtype, refused with --label_dtype bf16), --fused_bn (the training rounds'
+train_segnet.py --fused_bn: BatchNorm, ReLU, pooling and the classifier on fused kernels; passed to the training children
+only when given, with any --dtype and with --split_planes), --loader_procs (the training rounds'
 train_segnet.py --loader_procs: decode workers per rank and the input stage on the GPU, passed only when given; the
 job needs n_gpus x loader_procs CPUs for them; they also feed those rounds' validation), --label_loader_procs (the
 labelling passes' labels_from_segnet.py --loader_procs: decode workers per labelling process, independent of
@@ -99,6 +101,8 @@ def get_parser():
                         help="train_segnet.py --split_planes for the training rounds (float32 only)")
     parser.add_argument('--label_split_planes', action='store_true', default=False,
                         help="labels_from_segnet.py --split_planes for the labelling passes (--label_dtype fp32 only)")
+    parser.add_argument('--fused_bn', action='store_true', default=False,
+                        help="train_segnet.py --fused_bn for the training rounds")
     parser.add_argument('--loader_procs', type=int, default=0,
                         help="train_segnet.py --loader_procs for the training rounds: decode workers PER RANK "
                              "(keep n_gpus x loader_procs within the CPUs the job has); 0: none")
@@ -223,6 +227,8 @@ def train_argv(args, step, result_dir, dirs):
         a.append('--random')
     if args.split_planes:
         a.append('--split_planes')
+    if args.fused_bn:
+        a.append('--fused_bn')
     if args.loader_procs:
         a += ['--loader_procs', str(args.loader_procs)]
     return a
