@@ -9,7 +9,8 @@
 // spa_segnet_score follows unchanged.
 //
 // The bf16 staging and K loop (shared with spa_segnet_train_bf16.hip) are sg_conv_main_bf16 of spa_segnet_dev.h; this
-// file owns the kernel's LDS and launches, the weight workspace and the entry points.
+// file owns the kernel's LDS and launches, the weight workspace and the entry points.  Like that file it is compiled with
+// -fno-slp-vectorize (Makefile: conv1's LRN must not be packed into v_pk_*_f32 instructions).
 #include "spa_segnet_dev.h"
 
 // MODE SG_CONV1: X (B,3,H,W) float32 planar 0..255, Wb (7,64,32) bf16 = (K step, n, k), k = 4 (tap - 8 step) + c,

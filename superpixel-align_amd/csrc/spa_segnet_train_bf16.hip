@@ -7,8 +7,9 @@
 // and of the weights (rounded once per call into a packed bf16 copy in the context workspace).  The products are
 // v_mfma_f32_16x16x32_bf16 accumulating in float32; y, dx, the BN partial sums (float32 per workgroup, reduced in
 // float64 in block order) and dW (split-K, the chunks summed in chunk order in float64) are float32 as before.  No
-// atomics; the work split depends on the shape only, so the bits should not depend on the run or the device (observed
-// otherwise for conv1's forward at 2 x 256 x 512 and larger, cause unknown: profiles/segnet_refactor_digests.txt).
+// atomics; the work split depends on the shape only, so the bits do not depend on the run or the device.  This file and
+// spa_segnet_bf16.hip are compiled with -fno-slp-vectorize (Makefile): with conv1's LRN packed into v_pk_*_f32
+// instructions the staged operand was not the same in every call at grids of several workgroups per CU.
 //
 // Forward and dgrad run the bf16 staging and K loop shared with spa_segnet_bf16.hip (sg_conv_main_bf16 of
 // spa_segnet_dev.h).  This file owns the kernels' LDS and launches, the bf16 wgrad kernel and the bf16 weight packing.

@@ -32,6 +32,7 @@ Module names follow the upstream checkpoint (conv1/bn1/layerN.M.convK/downsample
 `drn_c_26-ddedf421.pth` / `drn_d_22-4bd2f8ea.pth` load with load_state_dict, and
 `models/drn_c_26.npz` (Chainer) loads through `load_chainer_npz`.
 """
+import gc
 import math
 import os
 
@@ -741,8 +742,19 @@ class DRN(nn.Module):
             if prof_was:
                 eng.prof_enable(False)              # (event records of the per-kernel timers do not belong into a graph)
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
-                g_out = pick(self._forward_chunk(g_in))
+            # A garbage collection inside the capture runs finalisers in this thread, and Engine.__del__ frees device memory
+            # (spa_ctx_destroy), which a capturing thread may not do: the capture is invalidated and the stream stays unusable.
+            # A driver called several times in one process leaves such engines behind in reference cycles.  So collect them
+            # now and let no collection start before the capture has ended.
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
+                    g_out = pick(self._forward_chunk(g_in))
+            finally:
+                if gc_was_on:
+                    gc.enable()
             delta = _epi_delta(snap)
             _epi_restore(snap)
             if delta.get('library_convs', 0) > 0 and os.environ.get('SPA_DRN_GRAPH') != '1':

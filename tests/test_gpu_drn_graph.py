@@ -134,3 +134,46 @@ def test_forty_batches_beside_the_superpixel_branch_graph_vs_eager(mods):
         assert np.array_equal(got['0'][1][s][0], got['auto'][1][s][0]) and np.array_equal(got['0'][1][s][1], got['auto'][1][s][1]), \
             'HostStream batch %d differs' % s
         assert np.array_equal(got['auto'][1][s][0], got['auto'][0][s][0])
+
+
+def test_capture_survives_an_unreachable_engine_and_a_collection_inside_it(mods):
+    """A driver that ran earlier in the process leaves its Engine behind in a reference cycle; Engine.__del__ frees device memory,
+    which the capturing thread may not do.  _graph_capture collects such garbage before it begins and holds the collector off
+    until the capture has ended: here the cycle is still uncollected when the capture is asked for, and the captured forward
+    itself asks for a collection, as an allocation threshold reached in the middle of it would."""
+    import gc
+    import weakref
+    mods.ops.engine()
+    model = mods.drn.create_drn('drn_d_22', device='cuda')
+    x = torch.from_numpy(mods.synth.synth_batch([5, 6], 96, 160)).cuda()
+    eager = _maps(model, x, '0')
+
+    class Finished(object):
+        pass
+    calls = []
+    forward = model._forward_chunk
+
+    def forward_with_a_collection(xc):
+        calls.append(torch.cuda.is_current_stream_capturing())
+        if calls[-1]:
+            gc.collect()
+        return forward(xc)
+    was_on = gc.isenabled()
+    gc.disable()                                         # (so that the cycle below lives until the capture is asked for)
+    try:
+        left = Finished()
+        left.engine, left.me = mods.engine.Engine(), left
+        dead = weakref.ref(left)
+        del left
+        assert dead() is not None
+        model._forward_chunk = forward_with_a_collection
+        graph = _maps(model, x, 'auto')                  # (a capture that fell back raises: _maps turns the warning into an error)
+        assert not gc.isenabled()                        # the collector is left as it was found
+    finally:
+        del model._forward_chunk
+        if was_on:
+            gc.enable()
+    assert calls == [False, False, True] and dead() is None
+    ents = list(model._graphs.values())
+    assert len(ents) == 1 and ents[0] is not False, 'the forward was not captured'
+    assert torch.equal(graph[7], eager[7]) and torch.equal(_maps(model, x, 'auto')[7], eager[7])

@@ -151,13 +151,12 @@ def test_refusals_launch_nothing(eng):
 
 
 # ------------------------------------------------------------------------------- whole network
-# conv1's float32 operand (standardisation + LRN, a powf per channel) is not bit-reproducible across compilation units:
-# at 2 x 512 x 1024 the bf16 roundings of the float32 training kernel's operand and of the bf16 training kernel's
-# differ at 24 of 3.1M values, and this kernel's differ from either at a similar rate.  Each such operand is one bf16
-# step off, so the full-size conv1 check allows a small fraction of outputs beyond LAYER_TOL, with a bounded error.
-# Measured (random_params(19), seed-20 image): 0.19 % of the 16.8M pooled values, worst 4.0e-4 of max|ref|.
-CONV1_FLIP_FRACTION = 5e-3
-CONV1_FLIP_TOL = 2e-3
+# conv1's bf16 operand is the bf16 rounding of the float32 training kernel's operand (sref.conv1_operand) bit for bit, in
+# every call and at every grid size (tests/test_gpu_segnet_exact.py; the bf16 files are built without packed float32
+# instructions in the LRN).  So the full-size conv1 check is the other layers': no output beyond
+# LAYER_TOL.  Before that build these two were 5e-3 and 2e-3 and absorbed operands one bf16 step off.
+CONV1_FLIP_FRACTION = 0.0
+CONV1_FLIP_TOL = LAYER_TOL
 # The free-running restatement starts from the device's conv1 output and then rounds each of its own float64 layer
 # outputs to bf16: a value that the float32 accumulation moves across a bf16 rounding boundary becomes another operand
 # (2^-8 relative), and with random weights these differences grow over the remaining seven layers until some pooling
