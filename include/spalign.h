@@ -548,6 +548,21 @@ int spa_segnet_encode_f16x3(spa_ctx *ctx, const float *x, int32_t x_layout, int3
 int spa_segnet_decode_f16x3(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B, int32_t Hh,
                             int32_t Wh, const float *wt, const float *bias, const float *wc, const float *bc, float *y,
                             void *stream);
+/* decode1 with the classifier's raw scores (segnet_basic.py:96-114: predict() without return_score resizes the scores
+ * BEFORE any softmax and takes their argmax; utils/create_demovideo.py): the arguments, layouts, alignment rules and
+ * refusal codes of spa_segnet_decode / _bf16 / _f16x3 with wc (2,64) and bc (2) REQUIRED (NULL: SPA_ERR_ARG).  y
+ * (B,2,2Hh,2Wh) float32 planar = the two classifier sums conv1x1(conv7x7(unpool(x, idx)) + bias; wc) + bc, the values
+ * the softmax of the decode entry points consumes, stored where they store the probabilities; everything before the
+ * store is their kernel.  The sums are defined at every decoder size, so 2Hh and 2Wh need not be multiples of 16. */
+int spa_segnet_decode_logits(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B, int32_t Hh,
+                             int32_t Wh, const float *wt, const float *bias, const float *wc, const float *bc, float *y,
+                             void *stream);
+int spa_segnet_decode_logits_bf16(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B,
+                                  int32_t Hh, int32_t Wh, const float *wt, const float *bias, const float *wc,
+                                  const float *bc, float *y, void *stream);
+int spa_segnet_decode_logits_f16x3(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout, int32_t B,
+                                   int32_t Hh, int32_t Wh, const float *wt, const float *bias, const float *wc,
+                                   const float *bc, float *y, void *stream);
 /* SegNetBasic.predict's tail (segnet_basic.py:101-106): prob (B,2,h,w) float32 resized to (H,W) as chainercv's PIL
  * backend does it (Image.resize(BILINEAR) per channel, mode 'F': double coefficients, a horizontal pass rounded to
  * float32, then the vertical pass; same bits), mask (B,H,W) uint8 = argmax over the two channels (ties: 0), scores
@@ -563,6 +578,18 @@ int spa_segnet_score(spa_ctx *ctx, const float *prob, int32_t B, int32_t h, int3
  * refusal of a downscale as spa_segnet_score: SPA_ERR_ARG, nothing launched.  No host synchronisation. */
 int spa_segnet_label_eval(spa_ctx *ctx, const float *prob, int32_t B, int32_t h, int32_t w, int32_t H, int32_t W,
                           const uint8_t *label_ids, uint8_t *mask, float *scores, int64_t *counts, void *stream);
+/* spa_segnet_score's mask and utils/create_movie.py's blend in one launch (utils/create_demovideo.py --out_video_fn).
+ * score (B,2,h,w) float32, logits or probabilities; mask (B,H,W) uint8 has spa_segnet_score's bits.  frames and blended
+ * (B,H,W,3) uint8: blended is the frame where mask == 0, and where mask == 1 each channel c is
+ * (uint8)(alpha * (double)color_host[c] + (1.0 - alpha) * (double)v): both products rounded before the sum (no FMA), the
+ * cast truncating -- numpy's img[pred == 1] = alpha * pred_color[pred == 1] + (1 - alpha) * img[pred == 1]
+ * (create_movie.py:33-37).  color_host: three bytes on the host, in the frames' channel order.  W % 4 == 0 and 4-byte
+ * aligned frames, mask and blended: dword loads and stores; otherwise bytes.  SPA_ERR_ARG with nothing launched: a
+ * downscale, alpha outside [0, 1] or NaN, a NULL pointer, blended overlapping frames.  No LDS, no atomics, no host
+ * synchronisation. */
+int spa_segnet_overlay(spa_ctx *ctx, const float *score, int32_t B, int32_t h, int32_t w, int32_t H, int32_t W,
+                       const uint8_t *frames, const uint8_t *color_host, double alpha, uint8_t *mask, uint8_t *blended,
+                       void *stream);
 
 /* ---- SegNet-Basic training input stage (train_segnet.py --loader_procs; csrc/spa_segnet_input.hip) --------------
  * What segnet_train.ZippedEstimatedCityscapesDataset.get_example computes on the host from a decoded frame, with

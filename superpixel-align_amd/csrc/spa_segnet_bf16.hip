@@ -27,7 +27,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_segnet_conv_bf16(const float *__
                                                                  const float *__restrict__ bc, float *__restrict__ Y,
                                                                  uint8_t *__restrict__ Yi, int H, int W, SgStd st)
 {
-    constexpr int IN = MODE == SG_DEC1 ? SG_DEC : MODE;                  // the input form
+    constexpr int IN = sg_input_form_of(MODE);                            // the input form
     __shared__ __attribute__((aligned(16))) unsigned short xs[SG_HPIX * sg_ps_bf16(IN)];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -97,6 +97,26 @@ extern "C" int spa_segnet_decode_bf16(spa_ctx *ctx, const float *x, const uint8_
     else
         hipLaunchKernelGGL(k_segnet_conv_bf16<SG_DEC>, grid, dim3(SG_THREADS), 0, s, x, idx, wb, bias, nullptr,
                            nullptr, y, nullptr, H, W, SgStd{});
+    SPA_LAUNCH_CHECK();
+    return SPA_OK;
+}
+
+extern "C" int spa_segnet_decode_logits_bf16(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout,
+                                             int32_t B, int32_t Hh, int32_t Wh, const float *wt, const float *bias,
+                                             const float *wc, const float *bc, float *y, void *stream)
+{
+    int rc = sg_check_decode("spa_segnet_decode_logits_bf16", ctx, x, idx, x_layout, B, Hh, Wh, wt, bias, wc, bc, y,
+                             true);
+    if (rc != SPA_OK) return rc;
+    const int H = 2 * Hh, W = 2 * Wh;
+    unsigned short *wb = nullptr;
+    rc = spa_ws_reserve(ctx, WS_SEGNET_WBF16, SG_W64 * sizeof(unsigned short), (void **)&wb);
+    if (rc != SPA_OK) return rc;
+    hipStream_t s = spa_stream(stream);
+    sg_launch_bf16_wpack64(s, wt, 0, wb);
+    SPA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_segnet_conv_bf16<SG_DEC1L>, sg_conv_grid(B, H, W), dim3(SG_THREADS), 0, s, x, idx, wb, bias, wc,
+                       bc, y, nullptr, H, W, SgStd{});
     SPA_LAUNCH_CHECK();
     return SPA_OK;
 }

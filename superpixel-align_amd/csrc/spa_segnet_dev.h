@@ -38,7 +38,10 @@ typedef __attribute__((address_space(3))) sg_s16x4 sg_lds_s16x4;
 #define SGW_TW 32                     // wgrad tile columns
 #define SGW_MAXCH 96                  // wgrad: chunks of K at most
 
-enum { SG_CONV1 = 0, SG_ENC = 1, SG_DEC = 2, SG_DEC1 = 3 };      // input / layer forms (training: the first three)
+enum { SG_CONV1 = 0, SG_ENC = 1, SG_DEC = 2, SG_DEC1 = 3, SG_DEC1L = 4 };   // input / layer forms (training: the first three)
+// the input form of a layer form: decode1, with the softmax (SG_DEC1) or with the raw classifier sums (SG_DEC1L), reads a
+// decoder's input
+constexpr int sg_input_form_of(int mode) { return mode == SG_DEC1 || mode == SG_DEC1L ? SG_DEC : mode; }
 enum { SG_FULL = 0, SG_POOLED = 1 };                             // training epilogues
 
 struct SgStd {
@@ -437,7 +440,7 @@ __device__ __forceinline__ void sg_conv_main_bf16(sg_f32x4 (&acc)[4][4], unsigne
 
 // Inference, on the float32 sums acc.  SG_CONV1 / SG_ENC: Y (B,H/2,W/2,64) = maxpool2x2(relu(acc + bias)) and Yi its
 // uint8 argmax (ky * 2 + kx, first maximum).  SG_DEC: Y (B,H,W,64) = acc + bias.  SG_DEC1: Y (B,2,H,W) planar =
-// softmax(conv1x1(acc + bias; wc (2,64)) + bc (2)).
+// softmax(conv1x1(acc + bias; wc (2,64)) + bc (2)).  SG_DEC1L: the same two sums, stored before the softmax.
 template <int MODE>
 __device__ __forceinline__ void sg_infer_epilogue(sg_f32x4 (&acc)[4][4], const float *bias, const float *wc,
                                                   const float *bc, float *Y, uint8_t *Yi, int b, int ty0, int tx0,
@@ -586,15 +589,17 @@ static int sg_check_encode(const char *fn, const spa_ctx *ctx, const float *x, i
 }
 
 // spa_segnet_decode*: (Hh, Wh) the pooled map's size
+// logits (spa_segnet_decode_logits*): the classifier is required, and the raw sums are defined at every decoder size
 static int sg_check_decode(const char *fn, const spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout,
                            int32_t B, int32_t Hh, int32_t Wh, const float *wt, const float *bias, const float *wc,
-                           const float *bc, const float *y)
+                           const float *bc, const float *y, bool logits = false)
 {
     SG_ARG(ctx && x && idx && wt && bias && y && B > 0 && B < 65536 && Hh > 0 && Wh > 0);
     SG_ARG((wc == nullptr) == (bc == nullptr));
+    SG_ARG(!logits || wc);
     const int H = 2 * Hh, W = 2 * Wh;
     // decode1 writes the network's output: the input size, a multiple of 16
-    SG_ARG(!wc || (H % 16 == 0 && W % 16 == 0));
+    SG_ARG(logits || !wc || (H % 16 == 0 && W % 16 == 0));
     SG_ARG((long long)H * W * 64 < (1ll << 31) && H / SG_TH < 65536);
     SG_ARG(sg_al16(x) && sg_al16(wt) && ((uintptr_t)idx & 3) == 0);
     if (x_layout != SPA_LAYOUT_NHWC) {

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(SG_THREADS, 2) void k_segnet_conv_f16x3(const float
                                                                      const int *__restrict__ ex, int H, int W,
                                                                      SgStd st)
 {
-    constexpr int IN = MODE == SG_DEC1 ? SG_DEC : MODE;                  // the input form
+    constexpr int IN = sg_input_form_of(MODE);                            // the input form
     __shared__ __attribute__((aligned(16))) unsigned short xs[SG_HPIX * sg_ps_split(IN)];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -180,6 +180,25 @@ extern "C" int spa_segnet_decode_f16x3(spa_ctx *ctx, const float *x, const uint8
     else
         hipLaunchKernelGGL(k_segnet_conv_f16x3<SG_DEC>, grid, dim3(SG_THREADS), 0, s, x, idx, wp, bias, nullptr,
                            nullptr, y, nullptr, ex, H, W, SgStd{});
+    SPA_LAUNCH_CHECK();
+    return SPA_OK;
+}
+
+extern "C" int spa_segnet_decode_logits_f16x3(spa_ctx *ctx, const float *x, const uint8_t *idx, int32_t x_layout,
+                                              int32_t B, int32_t Hh, int32_t Wh, const float *wt, const float *bias,
+                                              const float *wc, const float *bc, float *y, void *stream)
+{
+    int rc = sg_check_decode("spa_segnet_decode_logits_f16x3", ctx, x, idx, x_layout, B, Hh, Wh, wt, bias, wc, bc, y,
+                             true);
+    if (rc != SPA_OK) return rc;
+    const int H = 2 * Hh, W = 2 * Wh;
+    hipStream_t s = spa_stream(stream);
+    unsigned short *wp = nullptr;
+    int *ex = nullptr;
+    rc = sgx_prepare(ctx, s, x, (long long)Hh * Wh * 16, 64, B, H, W, SgStd{}, wt, &wp, &ex);
+    if (rc != SPA_OK) return rc;
+    hipLaunchKernelGGL(k_segnet_conv_f16x3<SG_DEC1L>, sg_conv_grid(B, H, W), dim3(SG_THREADS), 0, s, x, idx, wp, bias,
+                       wc, bc, y, nullptr, ex, H, W, SgStd{});
     SPA_LAUNCH_CHECK();
     return SPA_OK;
 }

@@ -48,6 +48,7 @@
     } else {
         // decode1: classifier over the 64 channels = this lane's four channels, then a butterfly over the 16 lanes of
         // the block (commutative pairwise sums: every lane of the group ends with the same bits), then the softmax
+        // (SG_DEC1) or the two sums as they are (SG_DEC1L)
         float w0[4], w1[4], bn[4];
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
@@ -83,12 +84,17 @@
 #pragma unroll
             for (int r = 1; r < 4; ++r)
                 if (fi == r) { za = z0[r]; zb = z1[r]; }
-            const float mx = za > zb ? za : zb;
-            const float e0 = expf(za - mx), e1 = expf(zb - mx);
-            const float sum = e0 + e1;
             const long long o = (long long)b * 2 * plane + (long long)(oy + (fi >> 1)) * W + x + (fi & 1);
-            Y[o] = e0 / sum;
-            Y[o + plane] = e1 / sum;
+            if (MODE == SG_DEC1L) {
+                Y[o] = za;
+                Y[o + plane] = zb;
+            } else {
+                const float mx = za > zb ? za : zb;
+                const float e0 = expf(za - mx), e1 = expf(zb - mx);
+                const float sum = e0 + e1;
+                Y[o] = e0 / sum;
+                Y[o + plane] = e1 / sum;
+            }
         }
     }
 }

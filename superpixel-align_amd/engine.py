@@ -846,34 +846,42 @@ class Engine(object):
                  self._s()))
         return pooled, idx
 
-    def segnet_decode(self, x, idx, wt, bias, wc=None, bc=None):
+    def segnet_decode(self, x, idx, wt, bias, wc=None, bc=None, logits=False, out=None):
         """One decoder stage, conv7x7(unpool(x, idx)) + bias: x (B,64,h,w) float32 and idx (B,64,h,w) uint8
         channels-last -> (B,64,2h,2w) float32 channels-last; with the classifier wc (2,64), bc (2) (decode1): softmax
-        probabilities (B,2,2h,2w) float32 planar."""
-        return self._segnet_decode(self._lib.spa_segnet_decode, x, idx, wt, bias, wc, bc)
+        probabilities (B,2,2h,2w) float32 planar, or with logits=True the classifier's two sums before the softmax
+        (spa_segnet_decode_logits; wc and bc required).  out: the caller's (B,2,2h,2w) buffer for a classifier form."""
+        return self._segnet_decode('spa_segnet_decode%s', x, idx, wt, bias, wc, bc, logits, out)
 
-    def segnet_decode_bf16(self, x, idx, wt, bias, wc=None, bc=None):
+    def segnet_decode_bf16(self, x, idx, wt, bias, wc=None, bc=None, logits=False, out=None):
         """segnet_decode on the bf16 matrix cores: the same float32 arguments and outputs, every product operand
         rounded to bf16 (round to nearest even), float32 accumulation, bias, classifier and softmax."""
-        return self._segnet_decode(self._lib.spa_segnet_decode_bf16, x, idx, wt, bias, wc, bc)
+        return self._segnet_decode('spa_segnet_decode%s_bf16', x, idx, wt, bias, wc, bc, logits, out)
 
-    def segnet_decode_f16x3(self, x, idx, wt, bias, wc=None, bc=None):
+    def segnet_decode_f16x3(self, x, idx, wt, bias, wc=None, bc=None, logits=False, out=None):
         """segnet_decode at float32 accuracy on the f16 matrix cores: the same float32 arguments and outputs, every
         operand as two scaled half-precision planes (one scale per image), float32 bias, classifier and softmax."""
-        return self._segnet_decode(self._lib.spa_segnet_decode_f16x3, x, idx, wt, bias, wc, bc)
+        return self._segnet_decode('spa_segnet_decode%s_f16x3', x, idx, wt, bias, wc, bc, logits, out)
 
-    def _segnet_decode(self, fn, x, idx, wt, bias, wc, bc):
+    def _segnet_decode(self, name, x, idx, wt, bias, wc, bc, logits=False, out=None):
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and idx.dtype == torch.uint8
         B, C, h, w = x.shape
         assert C == 64 and tuple(idx.shape) == tuple(x.shape)
         _req(wt, torch.float32, 'wt')
         _req(bias, torch.float32, 'bias')
+        if logits and (wc is None or bc is None):
+            raise SpalignError('segnet_decode: logits=True needs the classifier wc and bc')
+        fn = getattr(self._lib, name % ('_logits' if logits else ''))
         if wc is None:
+            if out is not None:
+                raise SpalignError('segnet_decode: out is for the classifier forms only')
             y = torch.empty((B, 64, 2 * h, 2 * w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
         else:
             _req(wc, torch.float32, 'wc')
             _req(bc, torch.float32, 'bc')
-            y = torch.empty((B, 2, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+            y = out if out is not None else torch.empty((B, 2, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+            if tuple(_req(y, torch.float32, 'out').shape) != (B, 2, 2 * h, 2 * w):
+                raise SpalignError('segnet_decode: out must be %s float32' % ((B, 2, 2 * h, 2 * w),))
         layout = self._layout(x)
         if self._layout(idx) != layout:
             raise SpalignError('segnet_decode: x and idx have different layouts')
@@ -914,6 +922,32 @@ class Engine(object):
         check(self._lib.spa_segnet_label_eval(self._ctx, _ptr(prob), B, h, w, H, W, _ptr(label_ids), _ptr(mask),
                                               _ptr(sc), _ptr(counts), self._s()))
         return mask, sc, counts
+
+    def segnet_overlay(self, score, frames, color=(128, 64, 128), alpha=0.5, out_mask=None, out_blended=None):
+        """segnet_score's mask of score (B,2,h,w) float32 at the frames' size and utils/create_movie.py's blend of the
+        road colour into frames (B,H,W,3) uint8, in one launch -> (mask (B,H,W) uint8, blended (B,H,W,3) uint8): where
+        the mask is 1 a channel is uint8(alpha * color[c] + (1 - alpha) * v) as numpy computes it (demovideo.blend_host),
+        elsewhere the frame's byte.  frames may be any view with contiguous (H,W,3) images packed one after the other;
+        out_mask / out_blended: the caller's buffers."""
+        score = _req(score, torch.float32, 'score')
+        frames = _req(frames, torch.uint8, 'frames')
+        B, C, h, w = score.shape
+        if C != 2 or frames.dim() != 4 or frames.shape[0] != B or frames.shape[3] != 3:
+            raise SpalignError('segnet_overlay: score must be (B,2,h,w) and frames (B,H,W,3), got %s and %s'
+                               % (tuple(score.shape), tuple(frames.shape)))
+        H, W = int(frames.shape[1]), int(frames.shape[2])
+        color = [int(v) for v in color]
+        if len(color) != 3 or min(color) < 0 or max(color) > 255:
+            raise SpalignError('segnet_overlay: color must be three values 0..255, got %r' % (color,))
+        mask = out_mask if out_mask is not None else torch.empty((B, H, W), dtype=torch.uint8, device=score.device)
+        blended = out_blended if out_blended is not None else torch.empty_like(frames)
+        if tuple(_req(mask, torch.uint8, 'out_mask').shape) != (B, H, W) or \
+                tuple(_req(blended, torch.uint8, 'out_blended').shape) != (B, H, W, 3):
+            raise SpalignError('segnet_overlay: out_mask must be %s and out_blended %s uint8' % ((B, H, W), (B, H, W, 3)))
+        check(self._lib.spa_segnet_overlay(self._ctx, _ptr(score), B, h, w, H, W, _ptr(frames),
+                                           (ctypes.c_uint8 * 3)(*color), float(alpha), _ptr(mask), _ptr(blended),
+                                           self._s()))
+        return mask, blended
 
     # ---- SegNet-Basic training input stage (segnet_loader.py): get_example's arithmetic on decoded batches
     def _input_tables(self, kind, n_in, n_out, backend):

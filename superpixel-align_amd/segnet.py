@@ -84,6 +84,14 @@ def load_snapshot(param_dir, iteration):
     read with numpy from the Chainer npz (keys 'updater/model:main/predictor/<link>/<param>')."""
     train_args = load_train_args(param_dir)
     snapshot = find_snapshot(param_dir, iteration)
+    return train_args, snapshot, read_snapshot(snapshot)
+
+
+def read_snapshot(snapshot):
+    """The parameters of one snapshot FILE (utils/create_demovideo.py --snapshot, which the reference loads with
+    serializers.load_npz(path='updater/model:main/predictor/')): load_snapshot's dictionary, with its checks of the
+    keys and shapes.  There is no args.txt to read beside a bare file: the network is taken to be SegNet-Basic, and a
+    snapshot of another model fails those checks."""
     want = {}
     for i, name in enumerate(LAYERS):
         want[name + '/W'] = (64, 3 if i == 0 else 64, 7, 7)
@@ -100,7 +108,7 @@ def load_snapshot(param_dir, iteration):
             if a.shape != shape:
                 raise ValueError('%s: %s has shape %s, expected %s' % (snapshot, PREFIX + key, a.shape, shape))
             params[key] = a
-    return train_args, snapshot, params
+    return params
 
 
 def fold_bn(params, dtype=np.float32):
@@ -276,10 +284,19 @@ class SegNetBasic(object):
         model.train_args, model.snapshot = train_args, snapshot
         return model
 
-    def forward(self, x, timer=None, trace=None):
-        """x (B,3,H,W) float32 0..255 on the device -> softmax probabilities (B,2,H,W) float32.  timer(name) is called
-        before each layer and at the end (per-layer event timing, tools/segnet_bench.py); trace (a list) receives the
-        encoders' (pooled, idx) pairs."""
+    @classmethod
+    def from_snapshot_file(cls, snapshot, pred_shape=None, device=None, dtype='fp32', split_planes=False):
+        """The network of one snapshot file (read_snapshot), as utils/create_demovideo.py --snapshot names it."""
+        check_mode('SegNetBasic', dtype, split_planes)
+        model = cls(read_snapshot(snapshot), pred_shape, device, dtype=dtype, split_planes=split_planes)
+        model.snapshot = snapshot
+        return model
+
+    def forward(self, x, timer=None, trace=None, logits=False):
+        """x (B,3,H,W) float32 0..255 on the device -> softmax probabilities (B,2,H,W) float32, or with logits=True the
+        classifier's raw scores (the values that softmax consumes).  timer(name) is called before each layer and at the
+        end (per-layer event timing, tools/segnet_bench.py); trace (a list) receives the encoders' (pooled, idx)
+        pairs."""
         e = self.engine
         B, C, H, W = x.shape
         if C != 3 or H % 16 or W % 16:
@@ -300,7 +317,7 @@ class SegNetBasic(object):
         for name, idx in zip(DECODERS, pools[::-1]):
             timer and timer(name)
             if name == 'conv_decode1':
-                h = decode(h, idx, self.w[name], self.b[name], self.wc, self.bc)
+                h = decode(h, idx, self.w[name], self.b[name], self.wc, self.bc, logits=logits)
             else:
                 h = decode(h, idx, self.w[name], self.b[name])
         timer and timer(None)
@@ -320,3 +337,14 @@ class SegNetBasic(object):
             return list(mask)
         sc = sc.cpu().numpy()
         return [(mask[i], sc[i]) for i in range(mask.shape[0])]
+
+    def predict_labels(self, imgs):
+        """What the reference's predict(imgs) returns WITHOUT return_score (segnet_basic.py:96-114,
+        utils/create_demovideo.py): the argmax of the classifier's raw scores resized to pred_shape with Pillow's
+        BILINEAR -- no softmax before the resize, where predict() above resizes probabilities.  The two differ where
+        the resize mixes pixels of different confidence.  imgs as for predict -> list of int32 (H',W') labels."""
+        import torch
+        x = torch.as_tensor(imgs, dtype=torch.float32).to(self.engine.device).contiguous()
+        z = self.forward(x, logits=True)
+        mask, _ = self.engine.segnet_score(z, self.pred_shape or tuple(z.shape[2:]))
+        return list(mask.cpu().numpy().astype(np.int32))
