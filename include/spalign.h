@@ -96,8 +96,14 @@ int spa_ws_generation(spa_ctx *ctx);
    EXTRA=-DSPA_DIAG only): k_slic_assign's shelved LDS-table variant, the reproducer of the co-residency miscompare (DESIGN.md section 7,
    tools/race_probe8.py) — never use it for results.  key 3: the stride-2 openers (spa_conv3x3_s2_f16s) on the 2-D tile kernel of
    spa_convs2.hip where it takes the shape (value 1, the default) or always on the generic kernel (value 0) — bit-identical outputs
-   either way.  No counterpart in the reference. */
+   either way.  key 4: the operand path of the Winograd layers — 0 = tiles numbered sub-grid by sub-grid and float32 V (the forms
+   before round 8), 1 = layers of dilation > 2 number their tiles with the sub-grids of a pixel row interleaved (consecutive tiles start at
+   consecutive pixels), 2 = that numbering and, in spa_conv3x3_wino4_f16s with Cout a multiple of 256 from 512 on, V written as the GEMM's half-precision planes (the default) — bit-identical
+   outputs for all three.  No counterpart in the reference. */
 int spa_debug_set(spa_ctx *ctx, int32_t key, int32_t value);
+/* diagnostics (tests/test_wino_numbering_cpu.py; host only, no GPU): out[5] = (image, sub-grid row, sub-grid column, tile row,
+   tile column) of tile t of the F(4x4,3x3) tiling of a (B,H,W) map, in the interleaved (interleaved != 0) or the sub-grid-major numbering. */
+int spa_wino4_tile_decode(int32_t B, int32_t H, int32_t W, int32_t dilation, int32_t interleaved, int64_t t, int32_t *out);
 /* diagnostics (tools/lds_probe.py): an LDS table filled and read back per lane, n_wg workgroups of 256 threads, out[n_wg][256][4];
    mode 0: 16-byte reads, 1: 4-byte reads, 2: broadcast reads.  No counterpart in the reference. */
 int spa_debug_lds_probe(spa_ctx *ctx, float *out, int32_t n_wg, int32_t steps, int32_t mode, void *stream);

@@ -124,11 +124,12 @@ struct spa_ctx {
     size_t conn_claim_bytes;
     int upd_wg_per_cu, upd_wg_per_cu8;
     int slic_force_general;      // SPA_SLIC_GENERAL=1 at context creation: spa_slic_core takes the general kernels
-    int zero_line_ready, conv_attr_done, conv32_attr_done, fz_attr_done, gemm16_attr_done, gemm16s_attr_done, nprng_attr_done;
+    int zero_line_ready, conv_attr_done, conv32_attr_done, fz_attr_done, gemm16_attr_done, gemm16s_attr_done, gemm16p_attr_done, nprng_attr_done;
     int rng_seeded;
     int ws_generation;             // counts workspace re-allocations (spa_ws_generation: captured graphs hold workspace addresses)
     int dbg_slic_ldsx;             // spa_debug_set key 2 (diagnostic builds: the reproducer variant of k_slic_assign)
     int convp_on;                  // spa_debug_set key 1 (spa_convp.hip instead of spa_conv32.hip's narrow tiles)
+    int wino_operands;             // spa_debug_set key 4: 0 = sub-grid-major tiles and float32 V, 1 = interleaved tile numbering (dilation > 2), 2 = + V as planes
     int convs2_on;                 // spa_debug_set key 3 (spa_convs2.hip's 2-D tile kernel for the stride-2 openers)
     int convs2_attr_done;
     int rs_key[4], rs_ks[2];       // bicubic tables held in WS_RESIZE_TAB: (H, W, h, w) and tap counts

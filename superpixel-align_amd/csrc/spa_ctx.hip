@@ -42,6 +42,7 @@ extern "C" int spa_ctx_create(int device, spa_ctx **out)
     if (const char *e = getenv("SPA_SLIC_GENERAL")) ctx->slic_force_general = atoi(e) != 0;
     ctx->convp_on = getenv("SPA_CONVP") ? atoi(getenv("SPA_CONVP")) != 0 : 1;
     ctx->convs2_on = 1;
+    ctx->wino_operands = 2;
     SPA_HIP(hipMalloc((void **)&ctx->d_status, 32 * sizeof(uint32_t)));        // [0] the bits, [16..31] ring of taken words
     SPA_HIP(hipMemset(ctx->d_status, 0, 32 * sizeof(uint32_t)));
     *out = ctx;
@@ -338,8 +339,9 @@ extern "C" int spa_ws_generation(spa_ctx *ctx) { return ctx ? ctx->ws_generation
 
 extern "C" int spa_debug_set(spa_ctx *ctx, int32_t key, int32_t value)
 {
-    SPA_ARG(ctx && (key == 1 || key == 2 || key == 3) && (value == 0 || value == 1));
+    SPA_ARG(ctx && (key == 1 || key == 2 || key == 3 || key == 4) && (value == 0 || value == 1 || (key == 4 && value == 2)));
     if (key == 1) ctx->convp_on = value;
+    else if (key == 4) ctx->wino_operands = value;
     else if (key == 3) ctx->convs2_on = value;
     else {
 #ifdef SPA_DIAG

@@ -18,10 +18,14 @@
 // channels 8q..8q+7, chunk 4 + q: their l).  X (the transformed activations V): plain float32, exactly what the float32
 // path's input transform writes (same bytes per element as two planes); a lane reads the 32 bytes of its 8 channels,
 // multiplies by the tile's power-of-two scale (position z: 2^(14 - e - p_i - p_j), e from the tracked maximum of the layer
-// input, spa_wino.hip) and splits in registers — 24 vector instructions per fragment next to 3 x MI matrix instructions
-// that consume it, so the split costs the matrix pipe nothing, and the input transform stays the streaming float32 kernel
-// (writing the planes from the transform was measured: 978 us instead of 608 per 15 images of a 512-channel layer, the
-// conversions serialise with its loads and stores at two waves per SIMD).  Staging (global_load_lds, XOR swizzle on the source address, two buffers, the next
+// input, spa_wino.hip) and splits in registers — 16 vector instructions per fragment next to 3 x MI matrix instructions that
+// consume it.  That is not free: every wave column of every channel tile splits the same element again, and without the split
+// the 512 -> 512 launch is 0.15-0.16 ms of 3.1 shorter (profiles/r8_wino_operands_ab.txt).  So from two channel tiles on (Cout >=
+// 512) the input transform writes V as the planes (k_wino4_in<..., PLANES>, the same split function, once per element) and
+// k_gemm_f16x3_stag<256, 256, PLANES> uses its fragment reads as they are; with one channel tile the gain is inside the spread and
+// V stays float32.  (An earlier attempt at planes from the transform, 978 us instead of 608 per 15 images of a 512-channel layer,
+// used packed conversions and two 8-byte stores per lane; the 8-byte stores alone cost 0.05-0.08 ms per 30 images — the shipped
+// form exchanges half chunks between neighbouring lanes and stores 16 bytes.)  Staging (global_load_lds, XOR swizzle on the source address, two buffers, the next
 // tile's first K step staged during the last K step, counted vmcnt over the epilogue stores, persistent workgroups on
 // XCD-contiguous tile ranges) is the float32 kernel's (spa_conv32.hip), tile 256 x 256 (or 128 x 128 for 128 output
 // channels), 8 waves; a lane's fragment is one 16-byte chunk per plane, and the K step of 32 channels is 3 x MI x NJ
@@ -35,6 +39,7 @@
 // fragments one fragment ahead, a quarter fragment (6 vector instructions) after every 6 matrix instructions with the order
 // pinned by scheduling barriers, changed nothing (3.53): the two waves of a SIMD already overlap each other's phases.
 #include "spa_common.h"
+#include "spa_wino_dev.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -242,7 +247,10 @@ __global__ __launch_bounds__(G16_THREADS, 2) void k_gemm_f16x3(const char *__res
 // stores issued behind them stay in flight) before the barrier that precedes the early half's R(q + 1).  Every accumulator
 // receives the same matrix instructions in the same order as in k_gemm_f16x3 (K steps ascending; l.h, h.l, h.h inside a
 // step): the outputs are bit-identical (tests/test_gpu_conv.py).
-template <int BM, int BN>
+// PLANES: X holds the planes already (k_wino4_in<..., PLANES> of spa_wino.hip scaled and split every element once): an 8-channel
+// chunk of 32 bytes is [8 x h][8 x l], so the same two 16-byte LDS reads of a lane ARE its fragment — no split, no scale, amax
+// is not read; staging, LDS image, swizzle and the order of the matrix instructions are unchanged (same bits).
+template <int BM, int BN, bool PLANES = false>
 __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__restrict__ X, const char *__restrict__ Wt,
                                                                  float *__restrict__ Y, int rows_per_z, int Cin, int Cout,
                                                                  int ntiles, int total_tiles, int zcount, long long xz,
@@ -254,8 +262,8 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
     const bool late = wave >= 4;
     const int all_i = zcount * total_tiles, gstep = (int)gridDim.x;
     const int nwg = total_tiles;
-    float sb;
-    {
+    float sb = 0.f;
+    if (!PLANES) {
         const unsigned bits = *amax;
         int e = (int)(bits >> 23) - 127;
         e = e < -100 ? -100 : (e > 100 ? 100 : e);
@@ -266,8 +274,7 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
     float zscale_s = 0.f;
     auto locate = [&](int vid) {
         const int z = vid / total_tiles;
-        const int zi = z / 6, zj = z - zi * 6;
-        const int psum = ((0x433444 >> (4 * zi)) & 15) + ((0x433444 >> (4 * zj)) & 15);
+        const int psum = wino4_psum(z);
         int id = vid - z * total_tiles;
         {
             const int q = nwg / 8, rem = nwg % 8, xcd = id % 8, idx = id / 8;
@@ -277,7 +284,7 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
         zz = __builtin_amdgcn_readfirstlane(z);
         r0 = __builtin_amdgcn_readfirstlane(pt * BN);
         n0 = __builtin_amdgcn_readfirstlane(nt * BM);
-        zscale_s = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sb * __uint_as_float((unsigned)(127 - psum) << 23))));
+        if (!PLANES) zscale_s = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sb * __uint_as_float((unsigned)(127 - psum) << 23))));
     };
     constexpr int WN = 4;
     constexpr int MI = BM == 256 ? 8 : 4;
@@ -371,24 +378,21 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
         // instructions later) the two low halves
         auto split_h = [&](int j, int e) {
             const float x0 = e < 2 ? ra[j][2 * e] : rb[j][2 * e - 4], x1 = e < 2 ? ra[j][2 * e + 1] : rb[j][2 * e - 3];
-            unsigned h;
-            asm volatile("v_fma_mixlo_f16 %0, %1, %3, 0 op_sel_hi:[0,0,0]\n\t"
-                         "v_fma_mixhi_f16 %0, %2, %3, 0 op_sel_hi:[0,0,0]"
-                         : "=&v"(h) : "v"(x0), "v"(x1), "s"(sc));
-            hu[j][e] = h;
+            hu[j][e] = wino_split_h(x0, x1, sc);
         };
         auto split_l = [&](int j, int e) {
             const float x0 = e < 2 ? ra[j][2 * e] : rb[j][2 * e - 4], x1 = e < 2 ? ra[j][2 * e + 1] : rb[j][2 * e - 3];
-            unsigned l;
-            asm volatile("v_fma_mixlo_f16 %0, %1, %3, -%4 op_sel_hi:[0,0,1]\n\t"
-                         "v_fma_mixhi_f16 %0, %2, %3, -%4 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-                         : "=&v"(l) : "v"(x0), "v"(x1), "s"(sc), "v"(hu[j][e]));
-            lu[j][e] = l;
+            lu[j][e] = wino_split_l(x0, x1, sc, hu[j][e]);
         };
+        if (PLANES) {
 #pragma unroll
-        for (int j = 0; j < RS; ++j)
+            for (int j = 0; j < NJ; ++j) { hu[j] = __builtin_bit_cast(u32x4, ra[j]); lu[j] = __builtin_bit_cast(u32x4, rb[j]); }
+        } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { split_h(j, e); split_l(j, e); }
+            for (int j = 0; j < RS; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { split_h(j, e); split_l(j, e); }
+        }
         // the late half's share of step q + 1 must have landed before the early half reads it behind this barrier (a tile's
         // stores drain in front of this wait; staging this share in front of them instead was measured no faster: DESIGN.md)
         if (late) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -410,7 +414,7 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[i], phj, acc[i][j], 0, 0, 0);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], plj, acc[i][j], 0, 0, 0);
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], phj, acc[i][j], 0, 0, 0);
-                if (j + RS < NJ) { if ((i & 1) == 0) split_h(j + RS, i >> 1); else split_l(j + RS, i >> 1); }
+                if (!PLANES && j + RS < NJ) { if ((i & 1) == 0) split_h(j + RS, i >> 1); else split_l(j + RS, i >> 1); }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -442,17 +446,21 @@ __global__ __launch_bounds__(G16_THREADS) void k_gemm_f16x3_stag(const char *__r
     }
 }
 
+// the tile of a GEMM with Cout output channels: only the 256 x 256 tile (the staggered kernel) has the form that takes planes
+int gemm_f16x3_tile(int32_t Cout) { return Cout % 256 == 0 ? 256 : 128; }
+
 // zcount = 36 problems  y[z] (rows, Cout) float32 = (scale_z x[z]) (rows, Cin) . wt[z]^T, wt[z] (Cout, Cin): x float32, wt in
 // the two-plane layout of the header (4 bytes per element); rows a multiple of 256, Cin a multiple of 32, Cout of 128;
 // amax: device word, bit pattern of a bound on the largest magnitude of the layer input (the scale's exponent)
 int gemm_f16x3_raw(spa_ctx *ctx, const float *x, long long rows, int32_t Cin, const void *wt, int32_t Cout, float *y,
-                   void *stream, int zcount, const void *amax)
+                   void *stream, int zcount, const void *amax, int planes)
 {
     SPA_ARG(ctx && x && wt && y && amax && rows > 0 && rows % 256 == 0 && rows < (1ll << 31) && zcount == 36);
     SPA_ARG(Cin % 32 == 0 && Cout % 128 == 0);
     SPA_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)wt % 16) == 0 && ((uintptr_t)y % 16) == 0);
     hipStream_t s = spa_stream(stream);
-    const int bm = Cout % 256 == 0 ? 256 : 128, bn = bm;
+    const int bm = gemm_f16x3_tile(Cout), bn = bm;
+    SPA_ARG(!planes || bm == 256);
     const int ntiles = Cout / bm;
     const long long total = rows / bn * ntiles;
     SPA_ARG(total < (1ll << 31));
@@ -467,6 +475,14 @@ int gemm_f16x3_raw(spa_ctx *ctx, const float *x, long long rows, int32_t Cin, co
             SPA_HIP(hipFuncSetAttribute((const void *)k_gemm_f16x3_stag<256, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
             ctx->gemm16s_attr_done = 1;
         }
+        if (planes) {
+            if (!ctx->gemm16p_attr_done) {
+                SPA_HIP(hipFuncSetAttribute((const void *)k_gemm_f16x3_stag<256, 256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
+                ctx->gemm16p_attr_done = 1;
+            }
+            hipLaunchKernelGGL((k_gemm_f16x3_stag<256, 256, true>), dim3((unsigned)grid), dim3(G16_THREADS), lds, s, (const char *)x, (const char *)wt, y,
+                               (int)rows, Cin, Cout, ntiles, (int)total, zcount, rows * Cin, (long long)Cout * Cin, rows * Cout, (const unsigned *)amax);
+        } else
         hipLaunchKernelGGL((k_gemm_f16x3_stag<256, 256>), dim3((unsigned)grid), dim3(G16_THREADS), lds, s, (const char *)x, (const char *)wt, y,
                            (int)rows, Cin, Cout, ntiles, (int)total, zcount, rows * Cin, (long long)Cout * Cin, rows * Cout, (const unsigned *)amax);
     } else {

@@ -25,6 +25,18 @@
 int conv1x1_f32_raw(spa_ctx *ctx, const float *x, long long rows, int32_t Cin, const float *wt, int32_t Cout,
                     float *y, void *stream, int zcount);          // spa_conv32.hip
 
+// the tile decode on the host, for the numbering test: out = (b, sy, sx, ty, tx) of tile t of the F(4x4) tiling
+extern "C" int spa_wino4_tile_decode(int32_t B, int32_t H, int32_t W, int32_t dilation, int32_t interleaved, int64_t t, int32_t *out)
+{
+    SPA_ARG(out && B > 0 && H > 0 && W > 0 && dilation >= 1);
+    WinoGeom g;
+    wino4_geom(B, H, W, dilation, &g);
+    SPA_ARG(t >= 0 && t < g.T);
+    g.interleaved = interleaved != 0;
+    wino_tile(g, t, out[0], out[1], out[2], out[3], out[4]);
+    return SPA_OK;
+}
+
 
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 f4sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
@@ -130,7 +142,7 @@ __global__ __launch_bounds__(256) void k_wino_out(const float *__restrict__ M, f
 
 static void wino_geom(int B, int H, int W, int d, WinoGeom *g)
 {
-    g->B = B; g->H = H; g->W = W; g->d = d;
+    g->B = B; g->H = H; g->W = W; g->d = d; g->interleaved = wino_interleave(d);
     const int hs = (H + d - 1) / d, ws = (W + d - 1) / d;         // the largest sub-grid
     g->th = (hs + 1) / 2; g->tw = (ws + 1) / 2;
     g->T = (long long)B * d * d * g->th * g->tw;
@@ -159,6 +171,7 @@ extern "C" int spa_conv3x3_wino_f32(spa_ctx *ctx, const float *x, int32_t B, int
     hipStream_t s = spa_stream(stream);
     WinoGeom g;
     wino_geom(B, H, W, dilation, &g);
+    g.interleaved = ctx->wino_operands >= 1 && wino_interleave(dilation);
     const long long Tpad = (g.T + 255) / 256 * 256;
     SPA_ARG(g.T * (Cin > Cout ? Cin : Cout) / 4 < (1ll << 31) * 256);
     {
@@ -207,9 +220,15 @@ extern "C" int spa_conv3x3_wino_f32(spa_ctx *ctx, const float *x, int32_t B, int
 // input patches overlap in both directions, was measured: no change — the overlap is served by L2 / MALL anyway —
 // and it padded small sub-grids to multiples of 4 tiles: 4x the work on a 7 x 7 sub-grid.  Row-major it is.)
 
-template <typename V>
+// PLANES (float4 only; the operand of k_gemm_f16x3_stag<..., PLANES>): every value is scaled by its position's exact power of
+// two 2^(14 - e - p_i - p_j), e from *amax, and written as the two half-precision planes the GEMM multiplies — the 32 bytes of
+// an 8-channel chunk become [8 x h][8 x l].  Same bytes per element and the same row pitch as the float32 form; the split is
+// the GEMM's own (wino_split_h / wino_split_l), done once per element.  (A thread's 4 channels are half of each plane of a
+// chunk: written as two 8-byte stores the kernel was 0.05-0.08 ms slower per 30 images of a 512-channel layer than the float32
+// form, with the halves exchanged between neighbouring lanes and ONE 16-byte store per lane it runs at the float32 form's time.)
+template <typename V, bool PLANES = false>
 __global__ __launch_bounds__(256) void k_wino4_in(const float *__restrict__ X, float *__restrict__ Vout, WinoGeom g, int C,
-                                                  long long Tpad)
+                                                  long long Tpad, const unsigned *__restrict__ amax = nullptr)
 {
     constexpr int VN = sizeof(V) / 4;
     const int c2 = C / VN;
@@ -240,7 +259,23 @@ __global__ __launch_bounds__(256) void k_wino4_in(const float *__restrict__ X, f
         wino4_bt(col, o);
 #pragma unroll
         // (non-temporal stores of V were measured: 1.60 instead of 1.31 ms per 30 images of a 512-channel layer)
-        for (int i = 0; i < 6; ++i) *(V *)(Vout + ((long long)(i * 6 + j) * Tpad + t) * C + c) = o[i];
+        for (int i = 0; i < 6; ++i) {
+            if constexpr (PLANES) {
+                static_assert(sizeof(V) == 16, "a thread owns half an 8-channel chunk");
+                const float sc = wino_pow2(14 - wino_amax_exp(*amax) - wino4_psum(i * 6 + j));
+                const unsigned h0 = wino_split_h(o[i].x, o[i].y, sc), h1 = wino_split_h(o[i].z, o[i].w, sc);
+                const unsigned l0 = wino_split_l(o[i].x, o[i].y, sc, h0), l1 = wino_split_l(o[i].z, o[i].w, sc, h1);
+                // chunk c / 8 of the row belongs to a pair of neighbouring lanes (C / 4 is even: same tile, both active): the even
+                // lane (channels c .. c + 3) takes the odd lane's h and stores the 16 bytes of h, the odd lane takes the even
+                // lane's l and stores the 16 bytes of l — one 16-byte store per lane, as in the float32 form
+                const bool odd = (c >> 2) & 1;
+                const unsigned r0 = wino_lane_swap(odd ? h0 : l0), r1 = wino_lane_swap(odd ? h1 : l1);
+                float *chunk = Vout + ((long long)(i * 6 + j) * Tpad + t) * C + (c & ~7);
+                *((uint4 *)chunk + (odd ? 1 : 0)) = odd ? make_uint4(r0, r1, l0, l1) : make_uint4(h0, h1, r0, r1);
+            } else {
+                *(V *)(Vout + ((long long)(i * 6 + j) * Tpad + t) * C + c) = o[i];
+            }
+        }
     }
 }
 
@@ -398,12 +433,14 @@ extern "C" int spa_conv3x3_wino4_f32(spa_ctx *ctx, const float *x, int32_t B, in
     hipStream_t s = spa_stream(stream);
     WinoGeom g;
     wino4_geom(B, H, W, dilation, &g);
+    g.interleaved = ctx->wino_operands >= 1 && wino_interleave(dilation);
     const long long Tpad = (g.T + 255) / 256 * 256;
     SPA_ARG(g.T * (Cin > Cout ? Cin : Cout) / 2 < (1ll << 31) * 256);
     {
         SpaProfScope prof_(ctx, PROF_WINO_IN, s);
         const long long n = g.T * (Cin / 4);
-        hipLaunchKernelGGL(k_wino4_in<float4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, v_scratch, g, Cin, Tpad);
+        hipLaunchKernelGGL((k_wino4_in<float4, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, v_scratch, g, Cin, Tpad,
+                           (const unsigned *)nullptr);
     }
     {
         int rc = conv1x1_f32_raw(ctx, v_scratch, Tpad, Cin, u, Cout, m_scratch, stream, 36);
@@ -424,7 +461,8 @@ extern "C" int spa_conv3x3_wino4_f32(spa_ctx *ctx, const float *x, int32_t B, in
 }
 
 int gemm_f16x3_raw(spa_ctx *ctx, const float *x, long long rows, int32_t Cin, const void *wt, int32_t Cout, float *y,
-                   void *stream, int zcount, const void *amax);          // spa_gemm16.hip
+                   void *stream, int zcount, const void *amax, int planes);          // spa_gemm16.hip
+int gemm_f16x3_tile(int32_t Cout);
 
 // amax[0] = bit pattern of max |x| over n floats (n a multiple of 4): the scale input of spa_conv3x3_wino4_f16s for a
 // tensor whose producer did not track it
@@ -456,6 +494,12 @@ extern "C" int spa_conv3x3_wino4_f16s(spa_ctx *ctx, const float *x, int32_t B, i
     hipStream_t s = spa_stream(stream);
     WinoGeom g;
     wino4_geom(B, H, W, dilation, &g);
+    g.interleaved = ctx->wino_operands >= 1 && wino_interleave(dilation);
+    // V as the GEMM's planes: the 256 x 256 tile's kernel takes them (spa_gemm16.hip), and they pay from two channel tiles on —
+    // the GEMM splits an element once per channel tile, and with ONE tile (256 -> 256, 30 images) taking the split out of it
+    // measured 0.01 ms of 0.96, inside the spread, next to +0.015 ms in the transform; with two tiles 0.06 (256 -> 512) and
+    // 0.16-0.18 ms (512 -> 512) for nothing in the transform (profiles/r8_wino_operands_ab.txt)
+    const int planes = ctx->wino_operands >= 2 && gemm_f16x3_tile(Cout) == 256 && Cout >= 512;
     const long long Tpad = (g.T + 255) / 256 * 256;
     SPA_ARG(g.T * (Cin > Cout ? Cin : Cout) / 4 < (1ll << 31) * 256);
     WinoScale sc;
@@ -464,10 +508,15 @@ extern "C" int spa_conv3x3_wino4_f16s(spa_ctx *ctx, const float *x, int32_t B, i
     {
         SpaProfScope prof_(ctx, PROF_WINO_IN, s);
         const long long n = g.T * (Cin / 4);
-        hipLaunchKernelGGL(k_wino4_in<float4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (float *)v_scratch, g, Cin, Tpad);
+        if (planes)
+            hipLaunchKernelGGL((k_wino4_in<float4, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (float *)v_scratch, g, Cin, Tpad,
+                               (const unsigned *)amax_in);
+        else
+            hipLaunchKernelGGL((k_wino4_in<float4, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (float *)v_scratch, g, Cin, Tpad,
+                               (const unsigned *)nullptr);
     }
     {
-        int rc = gemm_f16x3_raw(ctx, (const float *)v_scratch, Tpad, Cin, u2, Cout, m_scratch, stream, 36, amax_in);
+        int rc = gemm_f16x3_raw(ctx, (const float *)v_scratch, Tpad, Cin, u2, Cout, m_scratch, stream, 36, amax_in, planes);
         if (rc != SPA_OK) return rc;
     }
     {

@@ -691,7 +691,7 @@ class DRN(nn.Module):
         eng = E['engine']
         key = (tuple(x.shape), x.dtype, tuple(x.stride()), self.compute_dtype, tuple(sorted(keep)), E['split_gemm'], E['own_conv'],
                E['own_conv32'], E['winograd'], id(eng), self.use_fused_stem,
-               os.environ.get('SPA_WINO_MIN_CIN'))
+               os.environ.get('SPA_WINO_MIN_CIN'), eng.debug_get(4, 2))
         cache = self.__dict__.setdefault('_graphs', {})
         # a captured launch holds the addresses of libspalign's workspaces (packed stem weights, the zero line, ...): when one of
         # them has been re-allocated since (another model or a larger shape on the same context), every graph is stale

@@ -124,8 +124,15 @@ class Engine(object):
     def debug_set(self, key, value):
         """diagnostic kernel-selection switches (include/spalign.h: spa_debug_set); key 1 = planes-in-LDS kernel for the narrow
         split-plane 3x3 layers (1, default) or the kernel it replaced (0); key 3 = the 2-D tile kernel for the stride-2 openers
-        (conv3x3_s2_f16s; 1, default) or the generic kernel for every shape (0)"""
+        (conv3x3_s2_f16s; 1, default) or the generic kernel for every shape (0); key 4 = the Winograd layers' operand path:
+        0 = sub-grid-major tile numbering and float32 V, 1 = the sub-grids of a pixel row interleaved in the numbering (layers of
+        dilation > 2), 2 (default) = that numbering and V written as the GEMM's planes (Cout a multiple of 256 from 512 on)"""
         check(self._lib.spa_debug_set(self._ctx, int(key), int(value)))
+        self.__dict__.setdefault('_debug', {})[int(key)] = int(value)
+
+    def debug_get(self, key, default):
+        """the value debug_set last gave `key` on this engine (`default`: the library's own)"""
+        return self.__dict__.get('_debug', {}).get(int(key), default)
 
     # ------------------------------------------------------------------ per-kernel timing
     def prof_enable(self, on=True):
