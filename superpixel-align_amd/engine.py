@@ -643,15 +643,20 @@ class Engine(object):
                                           _ptr(cen), self._s()))
         return (labels, cen) if want_centres else labels
 
-    def felzenszwalb(self, rgb, scale=300.0, sigma=0.8, min_size=20, uint8_image=False):
+    def felzenszwalb(self, rgb, scale=300.0, sigma=0.8, min_size=20, uint8_image=False, out=None):
         """felzenszwalb(img/255, scale, sigma, min_size) for a batch -> labels (B,H,W) i32, n_labels (B).
         uint8_image: the reference passed a uint8 image, so /255. happens in float64
-        (superpixel_overlaps.py:294-300) instead of float32 (batch_spalign_kmeans.py:301-307)."""
+        (superpixel_overlaps.py:294-300) instead of float32 (batch_spalign_kmeans.py:301-307).
+        out: (labels, n_labels) tensors of the caller's to write into."""
         rgb = _req(rgb, torch.float32, 'rgb')
         B, C, H, W = rgb.shape
         assert C == 3
-        labels = torch.empty((B, H, W), dtype=torch.int32, device=rgb.device)
-        n_labels = torch.empty((B,), dtype=torch.int32, device=rgb.device)
+        if out is not None:
+            labels, n_labels = _req(out[0], torch.int32, 'labels'), _req(out[1], torch.int32, 'n_labels')
+            assert labels.shape == (B, H, W) and n_labels.shape == (B,)
+        else:
+            labels = torch.empty((B, H, W), dtype=torch.int32, device=rgb.device)
+            n_labels = torch.empty((B,), dtype=torch.int32, device=rgb.device)
         fn = self._lib.spa_felzenszwalb_u8 if uint8_image else self._lib.spa_felzenszwalb
         check(fn(self._ctx, _ptr(rgb), B, H, W, scale, sigma, min_size, _ptr(labels), _ptr(n_labels), self._s()))
         return labels, n_labels
