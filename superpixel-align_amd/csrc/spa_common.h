@@ -73,8 +73,8 @@ enum {
     WS_SRGB_LUT,     // sRGB companding of the 256 integer channel values
     WS_FZ_KEYS,      // felzenszwalb: edge cost keys (in/out of the radix sort)
     WS_FZ_VALS,      // felzenszwalb: edge indices (in/out of the radix sort)
-    WS_FZ_STATE,     // felzenszwalb: internal costs + reservation marks
-    WS_FZ_TMP,       // felzenszwalb: radix sort temporary storage
+    WS_FZ_STATE,     // felzenszwalb: internal costs, or for large images the 16-byte root records
+    WS_FZ_TMP,       // felzenszwalb: radix sort temporary storage, then the pass filters' block counts and segment words
     WS_STEM_WPACK,   // bf16 stem: weights packed in MFMA fragment order
     WS_ZERO_LINE,    // convolution: zero line read for padding pixels
     WS_RESIZE_TAB,   // input stage: bicubic tap tables of the current (input, output) size

@@ -32,14 +32,7 @@
 #ifndef FZ_THREADS
 #define FZ_THREADS 1024
 #endif
-#define FZ_EPT 1                 // edges per thread per window (1: a window of 1 024 sorted edges; larger windows only add serial work per round — measured 11.6 / 14.1 / 19.0 / 41 ms per 30 images of 224x224 for 1 / 2 / 4 / 8)
-
-#define FZ_MAXB 256               // images per launch (one resident workgroup each)
-struct FzImg {
-    unsigned barrier;            // monotonic arrival counter of this image's workgroup group
-    int cnt[4];                  // ring of group-wide counters (see fz_group_sum)
-    int pad[3];
-};
+#define FZ_MAXB 256               // images per launch (one workgroup each)
 
 // ---------------------------------------------------------------------------------------
 // host: scipy.ndimage._gaussian_kernel1d with the deterministic exp of the oracle
@@ -202,58 +195,12 @@ __global__ __launch_bounds__(256) void k_fz_costs(const double *__restrict__ sm,
 }
 
 __global__ void k_fz_init(int *__restrict__ parent, int *__restrict__ size, double *__restrict__ cint,
-                          unsigned long long *__restrict__ mark, long long total, FzImg *__restrict__ st, int B)
+                          long long total, int *__restrict__ diag)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        parent[i] = -1; size[i] = 1; cint[i] = 0.0; mark[i] = ~0ull;
+        parent[i] = -1; size[i] = 1; cint[i] = 0.0;
     }
-    if (blockIdx.x == 0 && (int)threadIdx.x < B) {
-        st[threadIdx.x].barrier = 0;
-        for (int i = 0; i < 4; ++i) st[threadIdx.x].cnt[i] = 0;
-        for (int i = 0; i < 3; ++i) st[threadIdx.x].pad[i] = 0;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 16) ((int *)((char *)st + FZ_MAXB * sizeof(FzImg)))[FZ_MAXB + threadIdx.x] = 0;    // pass diagnostics
-}
-
-__device__ __forceinline__ void fz_group_sync(unsigned *ctr, unsigned G, unsigned &epoch, uint32_t *status)
-{
-    if (G == 1u) {           // the whole image lives in one workgroup: a workgroup barrier is enough
-        __syncthreads();
-        return;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    epoch += 1;
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned target = epoch * G;
-        long long spins = 0;
-        while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > (1ll << 27)) { atomicOr(status, SPA_ST_KMEANS_BARRIER); break; }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-}
-
-// sum of `local` over all threads of the image's workgroup group (one barrier).  Counter slots
-// are used round-robin; the slot two steps ahead is cleared on the way (it was last read two
-// barriers ago).
-__device__ __forceinline__ int fz_group_sum(FzImg *me, unsigned &slot, int local, bool is_first_thread,
-                                            unsigned G, unsigned &epoch, uint32_t *status)
-{
-    if (G == 1u) return __syncthreads_or(local != 0);     // callers only test the sum against zero
-    int *c = &me->cnt[slot & 3u];
-    if (local) atomicAdd(c, local);
-    if (is_first_thread) __hip_atomic_store(&me->cnt[(slot + 2u) & 3u], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    fz_group_sync(&me->barrier, G, epoch, status);
-    const int total = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    slot += 1u;
-    return total;
+    if (blockIdx.x == 0 && threadIdx.x < 16) diag[threadIdx.x] = 0;    // pass diagnostics
 }
 
 // parent[] convention: -1 = root (self), otherwise the parent pixel (always a smaller index)
@@ -330,168 +277,21 @@ __global__ __launch_bounds__(256) void k_fz_zero_sizes(const int *__restrict__ z
     }
 }
 
-// One greedy pass (mode 0: merge test of the paper; mode 1: min_size clean-up) over the sorted
-// edges of every image; grid = (G, B), workgroups (., b) form the group of image b.
-template <bool LDSP>
-__global__ __launch_bounds__(FZ_THREADS) void k_fz_pass(const unsigned long long *__restrict__ keys,
-                                                        const unsigned *__restrict__ vals, FzGeom g,
-                                                        int *__restrict__ parent, int *__restrict__ size,
-                                                        double *__restrict__ cint,
-                                                        unsigned long long *__restrict__ mark,
-                                                        FzImg *__restrict__ st, double scale, int min_size,
-                                                        int mode, unsigned round0,
-                                                        const int *__restrict__ zcount, int flatten_every,
-                                                        uint32_t *__restrict__ status)
-{
-    const int b = blockIdx.y;
-    const unsigned G = gridDim.x;
-    const long long npix = (long long)g.H * g.W;
-    const unsigned long long *K = keys + (long long)b * g.nE;
-    const unsigned *V = vals + (long long)b * g.nE;
-    int *P = parent + (long long)b * npix;
-    int *S = size + (long long)b * npix;
-    double *CI = cint + (long long)b * npix;
-    unsigned long long *M = mark + (long long)b * npix;
-    FzImg *me = st + b;
-    unsigned epoch = me->barrier / G;             // barrier counter persists across launches
-    const long long T = (long long)G * FZ_THREADS;
-    const long long tg = (long long)blockIdx.x * FZ_THREADS + threadIdx.x;
-    unsigned round = round0;
-    unsigned slot = 0;
-    int win = 0;
-    // LDSP (images of <= 65 535 pixels, one workgroup per image): the parent array — the only pointer-chased
-    // state, two to three dependent round trips per endpoint and round — lives in LDS as 16-bit indices
-    // (0xFFFF = root) for the duration of the pass.
-    extern __shared__ unsigned short lpar[];
-    auto getp = [&](int i) -> int {
-        if (LDSP) { const unsigned v = lpar[i]; return v == 0xFFFFu ? -1 : (int)v; }
-        return P[i];
-    };
-    auto setp = [&](int i, int v) { if (LDSP) lpar[i] = (unsigned short)v; else P[i] = v; };
-    auto find = [&](int i) { int p; while ((p = getp(i)) >= 0) i = p; return i; };
-    if (LDSP) {
-        for (int p = (int)tg; p < (int)npix; p += FZ_THREADS) { const int q = P[p]; lpar[p] = q < 0 ? (unsigned short)0xFFFFu : (unsigned short)q; }
-        __syncthreads();
-    }
-
-    for (long long lo = zcount[b]; lo < g.nE; lo += T * FZ_EPT) {   // zero-cost edges: done up front
-        if (tg == 0) me->pad[2] += 1;                           // diagnostics: windows
-        // flattening the forest keeps the trees shallow; it costs a sweep over the image, so it is
-        // done every `flatten_every` windows (about once per npix/4 edges)
-        if ((win++ % flatten_every) == 0) {
-            for (long long p = tg; p < npix; p += T) {
-                int q = getp((int)p);
-                if (q >= 0) {
-                    int r = find(q);
-                    if (r != q) setp((int)p, r);
-                }
-            }
-        }
-        fz_group_sync(&me->barrier, G, epoch, status);
-        bool pend[FZ_EPT];
-        int ea[FZ_EPT], eb[FZ_EPT];
-        double cost[FZ_EPT];
-        // roots carried from round to round (round 4): a root of the last round is either still a root (one read) or has
-        // been linked to its new root by this window's merges (two or three reads) — the walk from the pixel through the
-        // forest of the last flattening is paid once per window, not once per round.  ea/eb hold the pixel, then the roots.
-        int ra[FZ_EPT], rb[FZ_EPT];
-#pragma unroll
-        for (int u = 0; u < FZ_EPT; ++u) {
-            const long long e = lo + tg + (long long)u * T;     // sorted position
-            pend[u] = e < g.nE;
-            if (pend[u]) {
-                fz_endpoints(g, (long long)V[e], ea[u], eb[u]);
-                cost[u] = __longlong_as_double((long long)K[e]);
-            }
-            ra[u] = ea[u]; rb[u] = eb[u];
-        }
-        for (;;) {
-            ++round;
-            if (tg == 0) me->pad[0] += 1;                       // diagnostics: rounds
-            const unsigned long long tag = (unsigned long long)(~round) << 32;
-            bool want[FZ_EPT], resv[FZ_EPT];
-            unsigned hold_a[FZ_EPT], hold_b[FZ_EPT];            // earliest reservation of either component, as last read
-            // ---- phase 1: roots and the merge test against the current state; edges that want
-            // to merge reserve both components with their position in the window
-#pragma unroll
-            for (int u = 0; u < FZ_EPT; ++u) {
-                want[u] = false; resv[u] = false;
-                hold_a[u] = hold_b[u] = 0xFFFFFFFFu;
-                if (!pend[u]) continue;
-                ra[u] = find(ra[u]);
-                rb[u] = find(rb[u]);
-                if (ra[u] == rb[u]) { pend[u] = false; continue; }      // same component for ever
-                if (mode == 0) {
-                    const float t0 = (float)(CI[ra[u]] + scale / (double)S[ra[u]]);
-                    const float t1 = (float)(CI[rb[u]] + scale / (double)S[rb[u]]);
-                    want[u] = cost[u] < (double)(t0 < t1 ? t0 : t1);
-                } else {
-                    want[u] = S[ra[u]] < min_size || S[rb[u]] < min_size;
-                }
-                if (want[u]) {
-                    const unsigned long long key = tag | (unsigned long long)(unsigned)(tg + (long long)u * T);
-                    atomicMin(M + ra[u], key);
-                    atomicMin(M + rb[u], key);
-                    resv[u] = true;
-                }
-            }
-            fz_group_sync(&me->barrier, G, epoch, status);
-            // ---- propagation: an edge that does not want to merge NOW may want to once an earlier
-            // reserved edge has changed one of its components, so while it waits it must hold its
-            // components too (later edges must not be decided against a state it might still change)
-            // (every pending edge reads the two reservation words in every step, also the ones that hold already: the step
-            // that changes nothing leaves the values the decision below needs — one dependent round trip less per round)
-            for (;;) {
-                int changed = 0;
-#pragma unroll
-                for (int u = 0; u < FZ_EPT; ++u) {
-                    if (!pend[u]) continue;
-                    const unsigned pos = (unsigned)(tg + (long long)u * T);
-                    const unsigned long long ma = __hip_atomic_load(M + ra[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned long long mb = __hip_atomic_load(M + rb[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned pa = (ma >> 32) == (tag >> 32) ? (unsigned)ma : 0xFFFFFFFFu;
-                    const unsigned pb = (mb >> 32) == (tag >> 32) ? (unsigned)mb : 0xFFFFFFFFu;
-                    hold_a[u] = pa; hold_b[u] = pb;
-                    if (resv[u]) continue;
-                    if (pa < pos || pb < pos) {
-                        const unsigned long long key = tag | (unsigned long long)pos;
-                        atomicMin(M + ra[u], key);
-                        atomicMin(M + rb[u], key);
-                        resv[u] = true;
-                        ++changed;
-                    }
-                }
-                if (tg == 0) me->pad[1] += 1;                   // diagnostics: propagation steps
-                if (fz_group_sum(me, slot, changed, tg == 0, G, epoch, status) == 0) break;
-            }
-            // ---- phase 2: decide every edge no earlier reservation can influence
-            int left = 0;
-#pragma unroll
-            for (int u = 0; u < FZ_EPT; ++u) {
-                if (!pend[u]) continue;
-                const unsigned pos = (unsigned)(tg + (long long)u * T);
-                const unsigned pa = hold_a[u], pb = hold_b[u];                   // read in the last (unchanged) propagation step
-                if (pa < pos || pb < pos) { ++left; continue; }                  // waits for an earlier edge
-                if (want[u]) {
-                    const int lo_r = min(ra[u], rb[u]), hi_r = max(ra[u], rb[u]);
-                    const int ns = S[ra[u]] + S[rb[u]];
-                    setp(hi_r, lo_r);
-                    S[lo_r] = ns;
-                    if (mode == 0) CI[lo_r] = cost[u];
-                }
-                pend[u] = false;
-            }
-            if (fz_group_sum(me, slot, left, tg == 0, G, epoch, status) == 0) break;
-        }
-    }
-    if (LDSP) {
-        __syncthreads();
-        for (int p = (int)tg; p < (int)npix; p += FZ_THREADS) { const unsigned v = lpar[p]; P[p] = v == 0xFFFFu ? -1 : (int)v; }
-    }
-}
-
 // ---------------------------------------------------------------------------------------
-// The pass with the state of the roots a window touches in LDS, one 1 024-thread workgroup per image.
+// One greedy pass (mode 0: merge test of the paper; mode 1: min_size clean-up) over the sorted edges of every image,
+// one 1 024-thread workgroup per image, with the state of the roots a window touches in LDS.
+//  * A window is 1 024 edges in sorted order, one per thread; an edge's position in the window is its rank in the
+//    sequential pass.  The window is played in rounds of three phases, until every edge is decided:
+//    1. every pending edge finds its two roots and evaluates the merge test against the current state; an edge that
+//       wants to merge reserves both components with atomicMin(position) on their reservation words.
+//    2. propagation, to a fixed point: an edge that does not want to merge NOW may want to once an earlier reserved
+//       edge has changed one of its components, so an edge that finds an earlier position on either of its components
+//       reserves both as well — while it waits it must HOLD its components, or a later edge would be decided against
+//       a state the waiting edge might still change.  The loop ends with the step in which no edge reserved anything:
+//       the reservation words that step read are final for the round, and they are what the decision needs.
+//    3. an edge is decided — its merge committed, or the edge dropped — iff no earlier position holds either of its
+//       components; otherwise it waits for the next round.  The earliest pending edge always decides, so a round
+//       always makes progress, and every edge is decided against exactly the state the sequential pass shows it.
 //  * LIVE edges only.  An edge whose endpoints already share a component can never merge anything (components only
 //    grow), and in the clean-up pass neither can an edge between two components of at least min_size pixels.  Most
 //    of the sorted list is dead by the time the pass reaches it (a 224x224 image: ~50 k merges out of 200 k edges;
@@ -504,18 +304,18 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass(const unsigned long long
 //    round costs workgroup barriers and LDS latencies instead of four or five dependent L2 round trips
 //    (~11 us -> ~2-3 us).  Merged components keep the cell of their surviving root (always one of the two that
 //    were entered); the cells go back to the global size / cost arrays when the window is done.
-//  * LPAR: images of <= 57 000 pixels keep the parent array in LDS as 16-bit indices as well (224x224, the
-//    reference's operating point); larger ones chase it through L2 (kept shallow by the flattening sweeps).
-// Decisions are those of k_fz_pass: same tests on the same values in the same order.
+//  * LPAR: images of <= 57 344 pixels keep the parent array in LDS as 16-bit indices as well (224x224, the
+//    reference's operating point).  Larger ones (!LPAR) chase it through L2 (kept shallow by the flattening sweeps)
+//    and differ in three more ways, all below: the window's own merges form a forest over the table's cells, the
+//    table is entered with one batch of loads of 16-byte root records, and chains of merges into one hub component
+//    are walked by one wave each.
 // ---------------------------------------------------------------------------------------
 #define FZL_EMPTY 0xFFFFFFFFu
 #ifndef FZ_CK
 #define FZ_CK 2
 #endif
-// one wave's LDS and global accesses have completed and are visible to its own lanes
-// Large images (round 5): a root's internal cost and size in ONE 16-byte record (the table pass fetches and writes back both per
-// root and window: one scattered access instead of two).  The records live where the internal costs and the legacy pass's
-// reservation words do (WS_FZ_STATE, 16 bytes per pixel: the table pass needs no reservation words in global memory).
+// Large images: a root's internal cost and size in ONE 16-byte record (the pass fetches and writes back both per root
+// and window: one scattered access instead of two).  The records fill WS_FZ_STATE, 16 bytes per pixel.
 struct __attribute__((aligned(16))) FzRec { double ci; int size; int pad; };
 __global__ __launch_bounds__(256) void k_fz_records(FzRec *__restrict__ rec, const int *__restrict__ size, long long n)
 {
@@ -549,6 +349,7 @@ __device__ __forceinline__ int fz_scan_min(int v)
     if (row >= 3) m = min(m, r2);
     return m;
 }
+// one wave's LDS and global accesses have completed and are visible to its own lanes
 __device__ __forceinline__ void fz_wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -561,29 +362,30 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
                                                             int *__restrict__ parent, int *__restrict__ size,
                                                             double *__restrict__ cint, double scale, int min_size,
                                                             int mode, const int *__restrict__ zcount,
-                                                            int flatten_every, int cells, int *__restrict__ diag, int hub_on = 0,
-                                                            const unsigned *__restrict__ idx = nullptr, int *__restrict__ seg = nullptr,
-                                                            int seg_div = 1, int skip_first_flatten = 0)
+                                                            int flatten_every, int cells, int *__restrict__ diag,
+                                                            const unsigned *__restrict__ idx, int *__restrict__ seg,
+                                                            int seg_div, int skip_first_flatten)
 {
     const int b = blockIdx.x;
     const int npix = g.H * g.W;
     const unsigned long long *K = keys + (long long)b * g.nE;
     const unsigned *V = vals + (long long)b * g.nE;
-    // large images (round 5): the pass walks a LIST of sorted positions — idx[b * nE + e] (idx == NULL: e itself) for e in
-    // [seg[2b], seg[2b + 1]) — and of that only the first 1 / seg_div: the prefilter kernels in front of fz_run cut pass 0 into
-    // segments and drop, between two segments and before the clean-up pass, every edge that can no longer merge anything
+    // the pass walks a LIST of sorted positions — idx[b * nE + e] (idx == NULL: e itself) for e in [seg[2b], seg[2b + 1]) — and
+    // of that only the first 1 / seg_div: the filter kernels in front of fz_run cut a large image's pass 0 into segments and
+    // drop, between two segments and before the clean-up pass, every edge that can no longer merge anything.  (seg == NULL, LPAR
+    // only: a small image's pass 0, one launch over every sorted position behind the zero-cost edges)
     const unsigned *IX = idx ? idx + (long long)b * g.nE : nullptr;
+    const bool listed = !LPAR || seg;
     long long nEb = g.nE, seg_start = -1;
-    if (seg) {
+    if (listed) {
         const long long st0 = seg[2 * b], n0 = seg[2 * b + 1];
         seg_start = st0;
         nEb = st0 + (n0 - st0 + seg_div - 1) / seg_div;
     }
     int *P = parent + (long long)b * npix;
-    int *S = size + (long long)b * npix;
+    int *S = size + (long long)b * npix;                      // LPAR: the roots' sizes and internal costs
     double *CI = cint + (long long)b * npix;
-    FzRec *SC = (FzRec *)cint + (long long)b * npix;          // !LPAR with hub_on bit 2: records instead of S / CI
-    const bool recs = !LPAR && (hub_on & 4);
+    FzRec *SC = (FzRec *)cint + (long long)b * npix;          // !LPAR: records instead of S / CI
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     extern __shared__ __attribute__((aligned(16))) unsigned char fzl[];
     unsigned short *lpar = (unsigned short *)fzl;
@@ -592,11 +394,11 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
     unsigned *lres = lkey + cells;                         // reservation: (tag << 10) | position in the window
     unsigned *lsz = lres + cells;                          // !LPAR only
     unsigned *wbuf = LPAR ? lsz : lsz + cells;             // the window: positions of its live edges in the sorted arrays
-    // !LPAR (round 5): the forest of the window's OWN merges over the table's cells — lcp[c] = the cell c's component was merged
+    // !LPAR: the forest of the window's OWN merges over the table's cells — lcp[c] = the cell c's component was merged
     // into (itself: still a root).  The rounds of a window then find their roots through LDS alone; the global parent array is
     // still written at every merge (the next window's set-up walks it) but never read inside a window's rounds
     unsigned short *lcp = (unsigned short *)(wbuf + FZ_THREADS);
-    // !LPAR, hub chains (round 5, below): pending edges per cell, hub slot per cell, the edges' cells / costs / decided flags,
+    // !LPAR, hub chains (below): pending edges per cell, hub slot per cell, the edges' cells / costs / decided flags,
     // per-hub bitmaps of the window positions that touch the hub
     constexpr int NHUB = 16, HUB_TH = 4;
     unsigned short *lcnt = lcp + cells;
@@ -636,22 +438,20 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
             h = h + 1 == cells ? 0 : h + 1;
         }
     };
-    auto enter = [&](int root) -> int {
+    auto enter = [&](int root) -> int {                    // LPAR
         int h = hash(root);
         for (;;) {
             unsigned w = __hip_atomic_load(lkey + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             if (w == FZL_EMPTY) {
-                w = atomicCAS(lkey + h, FZL_EMPTY, LPAR ? (unsigned)root << 16 : (unsigned)root);
+                w = atomicCAS(lkey + h, FZL_EMPTY, (unsigned)root << 16);
                 if (w == FZL_EMPTY) {                       // this thread's cell: fetch the root's state
-                    if (LPAR) __hip_atomic_store(lkey + h, ((unsigned)root << 16) | (unsigned)S[root], __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-                    else if (recs) { const FzRec q = SC[root]; lsz[h] = (unsigned)q.size; lci[h] = q.ci; return h; }
-                    else lsz[h] = (unsigned)S[root];
+                    __hip_atomic_store(lkey + h, ((unsigned)root << 16) | (unsigned)S[root], __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
                     if (mode == 0) lci[h] = CI[root];
                     return h;
                 }
             }
-            if (keyroot(w) == (unsigned)root) return h;
+            if ((w >> 16) == (unsigned)root) return h;
             h = h + 1 == cells ? 0 : h + 1;
         }
     };
@@ -673,12 +473,12 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
     }
     __syncthreads();
 
-    int win = skip_first_flatten ? 1 : 0, chunks = 0, rounds = 0, trounds = 0;      // (the prefilter has just flattened the forest)
+    int win = skip_first_flatten ? 1 : 0, chunks = 0, rounds = 0, trounds = 0;      // (the filter has just flattened the forest)
     long long tc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // diagnostics: cycles of flatten + write-back | collect | window set-up (table entry) | full rounds | tail | (of the rounds) propagation | hub chains | (set-up) table reset + cost loads
     int props = 0;
     long long t_ = (long long)__builtin_readcyclecounter();
 #define FZ_T(i) { const long long n_ = (long long)__builtin_readcyclecounter(); tc[i] += n_ - t_; t_ = n_; }
-    long long cursor = seg ? seg_start : zcount[b];         // zero-cost edges: done up front
+    long long cursor = listed ? seg_start : zcount[b];      // zero-cost edges: done up front
     unsigned vpre[FZ_CK], opre[FZ_CK];                      // edge indices and sorted-array positions of the next step
     long long vpre_at = -1;
     int step_par = 0;
@@ -739,7 +539,7 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
                     }
                 }
             } else {
-                // parent array in global memory (round 5): the 2 FZ_CK walks of a thread advance LEVEL BY LEVEL — every level is one
+                // parent array in global memory: the 2 FZ_CK walks of a thread advance LEVEL BY LEVEL — every level is one
                 // batch of independent loads instead of 2 FZ_CK dependent chains one after the other — and an edge whose endpoints
                 // point at the same parent is dead without looking further (most sorted positions of a late pass are: after a
                 // flattening sweep both pixels point straight at their root)
@@ -772,8 +572,7 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
                 if (mode == 1) {
 #pragma unroll
                     for (int k = 0; k < FZ_CK; ++k)
-                        if (live[k]) live[k] = recs ? (SC[ea_[k]].size < min_size || SC[eb_[k]].size < min_size)
-                                                    : (S[ea_[k]] < min_size || S[eb_[k]] < min_size);
+                        if (live[k]) live[k] = SC[ea_[k]].size < min_size || SC[eb_[k]].size < min_size;
                 }
             }
 #pragma unroll
@@ -823,31 +622,23 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
         if (pend) {
             if (LPAR) { ra = find(ea); rb = find(eb); }
             if (ra == rb) pend = false;                     // same component for ever
-            else if (!LPAR && (hub_on & 2)) {
-                // both cells claimed first, then the (up to four) loads of the roots' state in one batch: one global round trip
-                // per window set-up instead of two (62 -> 31 M cycles of set-up per full-size image; SPA_FZ_HUB=1 keeps enter()).
+            else if (!LPAR) {
+                // both cells claimed first, then the two loads of the roots' records in one batch: one global round trip per
+                // window set-up instead of two (62 -> 31 M cycles of set-up per full-size image).
                 // Measured and NOT kept: fetching the next step's first level of parents before the rounds (-15 M cycles of collect,
                 // +15 M here: the single compute unit's gather rate is the bound, not the latency of a level)
                 bool oa = false, ob = false;
                 ca = claim(ra, oa); cb = claim(rb, ob);
-                unsigned sa = 0, sb = 0;
-                double cia = 0.0, cib = 0.0;
-                if (recs) {
-                    FzRec qa, qb;
-                    qa.ci = qb.ci = 0.0; qa.size = qb.size = 0;
-                    if (oa) qa = SC[ra];
-                    if (ob) qb = SC[rb];
-                    sa = (unsigned)qa.size; cia = qa.ci; sb = (unsigned)qb.size; cib = qb.ci;
-                } else {
-                    if (oa) { sa = (unsigned)S[ra]; if (mode == 0) cia = CI[ra]; }
-                    if (ob) { sb = (unsigned)S[rb]; if (mode == 0) cib = CI[rb]; }
-                }
-                if (oa) { lsz[ca] = sa; if (mode == 0) lci[ca] = cia; }
-                if (ob) { lsz[cb] = sb; if (mode == 0) lci[cb] = cib; }
+                FzRec qa, qb;
+                qa.ci = qb.ci = 0.0; qa.size = qb.size = 0;
+                if (oa) qa = SC[ra];
+                if (ob) qb = SC[rb];
+                if (oa) { lsz[ca] = (unsigned)qa.size; if (mode == 0) lci[ca] = qa.ci; }
+                if (ob) { lsz[cb] = (unsigned)qb.size; if (mode == 0) lci[cb] = qb.ci; }
             }
             else { ca = enter(ra); cb = enter(rb); }
         }
-        if (!LPAR && (hub_on & 1)) e_cost[tid] = cost;
+        if (!LPAR) e_cost[tid] = cost;
         __syncthreads();
         FZ_T(2)
         for (unsigned round = 0;; ++round) {
@@ -907,7 +698,7 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
                 if (__syncthreads_or(changed) == 0) break;
             }
             FZ_T(5)
-            // ---- hub chains (!LPAR, round 5).  On a smooth full-size image nearly every live edge of a late window joins a
+            // ---- hub chains (!LPAR).  On a smooth full-size image nearly every live edge of a late window joins a
             // small component to ONE giant one; the protocol above decides the earliest of them per round (the others wait for
             // its reservation), 50 rounds per window.  Their decisions are a recurrence over the hub's state alone — internal
             // cost = the last merged edge's, size = the running sum — whenever the other side of each edge is touched by NO other
@@ -917,7 +708,7 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
             // hub walks the bitmap in window order — exactly the sequential pass over those edges — and stops at the first edge whose
             // other side has company.  Walked edges are decided (merged with the state written as phase 2 writes it, or dropped);
             // the rest of the round proceeds as before.
-            if (!LPAR && (hub_on & 1) && round >= 1) {
+            if (!LPAR && round >= 1) {
                 for (int i = tid; i < cells; i += FZ_THREADS) { lcnt[i] = 0; lslot[i] = 0; }
                 if (tid < NHUB * (FZ_THREADS / 32)) hbits[tid] = 0u;
                 if (tid == 0) *nhub = 0;
@@ -974,7 +765,7 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
                             ecost = e_cost[pp];
                         }
                         unsigned long long mask = __ballot(bit);
-                        // (round 5, later) the walk in RUNS.  Nearly every walked edge of a late window merges, so the lanes
+                        // the walk in RUNS.  Nearly every walked edge of a late window merges, so the lanes
                         // decide all at once under the assumption that every earlier edge of the block merged — the hub's size
                         // before lane i is then the hub's plus a prefix sum of leaf sizes, its root a prefix minimum of leaf
                         // roots, its internal cost the previous edge's — and the assumption is TRUE for every lane up to the
@@ -1198,7 +989,7 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
         for (int i = tid; i < cells; i += FZ_THREADS) {
             const unsigned w = lkey[i];
             if (w != FZL_EMPTY) {
-                if (recs) {
+                if (!LPAR) {
                     if (mode == 0) { FzRec r; r.ci = lci[i]; r.size = (int)csize(i); r.pad = 0; SC[keyroot(w)] = r; }
                     else SC[keyroot(w)].size = (int)csize(i);
                 } else {
@@ -1213,7 +1004,7 @@ __global__ __launch_bounds__(FZ_THREADS) void k_fz_pass_tab(const unsigned long 
         __syncthreads();
         for (int p = tid; p < npix; p += FZ_THREADS) { const unsigned v = lpar[p]; P[p] = v == 0xFFFFu ? -1 : (int)v; }
     }
-    if (tid == 0 && seg) seg[2 * b] = (int)nEb;             // the next segment (or the filter in front of it) starts here
+    if (tid == 0 && listed) seg[2 * b] = (int)nEb;            // the next segment (or the filter in front of it) starts here
     if (tid == 0 && diag) {
         atomicAdd(diag + 0, win); atomicAdd(diag + 1, chunks); atomicAdd(diag + 2, rounds); atomicAdd(diag + 3, trounds);
         for (int i = 0; i < 8; ++i) atomicAdd(diag + 4 + i, (int)(tc[i] >> 10));
@@ -1296,30 +1087,12 @@ __global__ __launch_bounds__(256) void k_fz_relabel(const int *__restrict__ pare
         out[(long long)b * npix + p] = R[fz_find(P, p)];
 }
 
-static int fz_run(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t W, double scale,
-                  double sigma, int32_t min_size, int32_t *labels, int32_t *n_labels, void *stream,
-                  bool wide);
-
-extern "C" int spa_felzenszwalb(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t W,
-                                double scale, double sigma, int32_t min_size, int32_t *labels,
-                                int32_t *n_labels, void *stream)
-{
-    return fz_run(ctx, rgb, B, H, W, scale, sigma, min_size, labels, n_labels, stream, false);
-}
-
-extern "C" int spa_felzenszwalb_u8(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t W,
-                                   double scale, double sigma, int32_t min_size, int32_t *labels,
-                                   int32_t *n_labels, void *stream)
-{
-    return fz_run(ctx, rgb, B, H, W, scale, sigma, min_size, labels, n_labels, stream, true);
-}
-
-// ---- filters of a large image's passes (round 5).  The passes' single workgroup spent half its time testing sorted positions
-// whose endpoints already share a component (and, in the clean-up pass, all 8.4 M positions again for the handful of edges that
-// touch a component below min_size).  Dead edges stay dead — components only grow —, so every compute unit drops them ahead of
-// the pass: the forest is flattened, the survivors of the list's unprocessed part are counted per block of 1 024 list
-// positions, scanned, and their positions in the sorted list written out in order.  Pass 0 runs as SPA_FZ_SEGMENTS launches with
-// such a filter between two of them, the clean-up pass as one launch behind a filter over the whole sorted list.
+// ---- filters of the passes.  A pass's single workgroup would spend half its time testing sorted positions whose endpoints
+// already share a component (and, in the clean-up pass, all 8.4 M positions of a full-size image again for the handful of edges
+// that touch a component below min_size).  Dead edges stay dead — components only grow —, so every compute unit drops them ahead
+// of the pass: the forest is flattened, the survivors of the list's unprocessed part are counted per block of 1 024 list
+// positions, scanned, and their positions in the sorted list written out in order.  A large image's pass 0 runs as several
+// launches with such a filter between two of them, every clean-up pass as one launch behind a filter over the whole sorted list.
 __global__ __launch_bounds__(256) void k_fz_flatten_all(int *__restrict__ parent, int npix)
 {
     int *P = parent + (long long)blockIdx.y * npix;
@@ -1440,9 +1213,9 @@ static int fz_run(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t 
     SPA_ARG(ctx && rgb && labels && n_labels && B > 0 && H > 1 && W > 1 && sigma > 0.0 && scale > 0.0);
     SPA_ARG((long long)H * W < (1ll << 28));
     {
-        // the persistent passes need every workgroup resident: at most n_cu images per launch
-        // (one workgroup per image: 256 full-size images in one launch keep every CU busy — 64 per launch measured
-        // 12.6 ms per image amortised, see HISTORY.md section 7; SPA_FZ_MAXB for experiments)
+        // one workgroup per image and pass: at most n_cu images per launch, a compute unit each
+        // (256 full-size images in one launch keep every CU busy — 64 per launch measured 12.6 ms per image amortised,
+        // see HISTORY.md section 7; SPA_FZ_MAXB: a smaller limit, so that tests reach the split with three images)
         int maxB = ctx->n_cu < FZ_MAXB ? ctx->n_cu : FZ_MAXB;
         if (const char *e = getenv("SPA_FZ_MAXB")) { const int v = atoi(e); if (v > 0 && v < maxB) maxB = v; }
         if (B > maxB) {
@@ -1469,10 +1242,9 @@ static int fz_run(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t 
 
     // workspaces (the connectivity pass of SLIC is not running at the same time: share its slots)
     double *sm0, *sm1, *cint;
-    unsigned long long *keys0, *keys1, *mark;
+    unsigned long long *keys0, *keys1;
     unsigned *vals0, *vals1;
-    int *parent, *size, *rank, *blk;
-    FzImg *st;
+    int *parent, *size, *rank, *blk, *zcount;
     void *tmp;
     int rc;
     const size_t planes = (size_t)B * 3 * npix * 8;
@@ -1487,16 +1259,21 @@ static int fz_run(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t 
     if ((rc = spa_ws_reserve(ctx, WS_SIZE, (size_t)B * npix * 4, (void **)&size)) != SPA_OK) return rc;
     if ((rc = spa_ws_reserve(ctx, WS_FINAL, (size_t)B * npix * 4, (void **)&rank)) != SPA_OK) return rc;
     if ((rc = spa_ws_reserve(ctx, WS_FZ_STATE, (size_t)B * npix * 16, (void **)&cint)) != SPA_OK) return rc;
-    mark = (unsigned long long *)(cint + (size_t)B * npix);
     if ((rc = spa_ws_reserve(ctx, WS_BLK, (size_t)B * 2 * nblk * 4, (void **)&blk)) != SPA_OK) return rc;
-    if ((rc = spa_ws_reserve(ctx, WS_CONNMISC, FZ_MAXB * sizeof(FzImg) + (FZ_MAXB + 64) * sizeof(int), (void **)&st)) != SPA_OK) return rc;
+    // zcount[FZ_MAXB], then the 16 diagnostic words of the passes (spa_debug_peek)
+    if ((rc = spa_ws_reserve(ctx, WS_CONNMISC, (FZ_MAXB + 16) * sizeof(int), (void **)&zcount)) != SPA_OK) return rc;
+    int *diag = zcount + FZ_MAXB;
     size_t tmp_bytes = 0;
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys0, keys1, vals0, vals1, (int)g.nE, 0, 64, s);
     tmp_bytes = (tmp_bytes + 255) & ~(size_t)255;
     // small images: a sort of a few hundred thousand keys is ~8 short launches, so a batch of sorts is launch
     // bound on one stream — they are dealt to three streams (own scratch each)
     const bool par_sort = B > 2 && g.nE <= (1ll << 21);
-    if ((rc = spa_ws_reserve(ctx, WS_FZ_TMP, tmp_bytes * (par_sort ? 3 : 1), &tmp)) != SPA_OK) return rc;
+    // the sorts are done when the passes start: their scratch then holds the filters' block counts (one per 1 024 sorted
+    // positions) and segment words (three pairs per image)
+    const int nblk_e = (int)((g.nE + 1023) / 1024);
+    const size_t sort_bytes = tmp_bytes * (par_sort ? 3 : 1), filter_bytes = (size_t)B * nblk_e * 4 + (size_t)B * 32;
+    if ((rc = spa_ws_reserve(ctx, WS_FZ_TMP, sort_bytes > filter_bytes ? sort_bytes : filter_bytes, &tmp)) != SPA_OK) return rc;
     if (par_sort && (rc = spa_aux_streams(ctx)) != SPA_OK) return rc;
 
     int gx = (int)((npix + 255) / 256);
@@ -1524,99 +1301,68 @@ static int fz_run(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t 
         SPA_HIP(hipStreamWaitEvent(s, ctx->ev_join[0], 0));
         SPA_HIP(hipStreamWaitEvent(s, ctx->ev_join[1], 0));
     }
-    hipLaunchKernelGGL(k_fz_init, dim3(1024), dim3(256), 0, s, parent, size, cint, mark, (long long)B * npix, st, B);
-    int *zcount = (int *)((char *)st + FZ_MAXB * sizeof(FzImg));
+    hipLaunchKernelGGL(k_fz_init, dim3(1024), dim3(256), 0, s, parent, size, cint, (long long)B * npix, diag);
     hipLaunchKernelGGL(k_fz_zero_count, dim3(B), dim3(64), 0, s, (const unsigned long long *)keys1, g.nE, zcount);
     hipLaunchKernelGGL(k_fz_zero_union, dim3(256, B), dim3(256), 0, s, (const unsigned *)vals1, g,
                        (const int *)zcount, parent);
     hipLaunchKernelGGL(k_fz_zero_sizes, dim3((unsigned)((npix + 255) / 256), B), dim3(256), 0, s,
                        (const int *)zcount, parent, size, (int)npix);
-    // persistent passes: every workgroup of the grid must be resident (one per CU at most)
-    // The passes are bound by the number of reservation rounds (chains of dependent merges), not by
-    // work per round: ONE 1024-thread workgroup per image makes a round cost a workgroup barrier
-    // (~1 us) instead of an agent-scope barrier across workgroups (~10 us each, several per round).
-    // SPA_FZ_GROUP overrides (experiments).
-    int G = 1;
-    if (const char *e = getenv("SPA_FZ_GROUP")) G = atoi(e) > 0 ? atoi(e) : 1;
-    if ((long long)G * B > ctx->n_cu) G = ctx->n_cu / B > 0 ? ctx->n_cu / B : 1;
-    SPA_ARG((long long)G * B <= ctx->n_cu);
-    long long fdiv = 4;          // about 4 sweeps per image worth of edges (measured: 2-4 best, 16+ slower)
-    if (const char *e = getenv("SPA_FZ_FLATTEN_DIV")) fdiv = atoi(e) > 0 ? atoi(e) : 4;       // experiments
-    long long fe = npix / (fdiv * G * FZ_THREADS * FZ_EPT);
+    // The passes are bound by the number of reservation rounds (chains of dependent merges), not by work per round:
+    // ONE 1 024-thread workgroup per image makes a round cost workgroup barriers (~1 us each).
+    const long long fe = npix / (4 * FZ_THREADS);      // about 4 flattening sweeps per image worth of edges (measured: 2-4 best, 16+ slower)
     const int flatten_every = fe < 1 ? 1 : (int)fe;
     // scale = float(scale) / 255.
     const double k = scale / 255.0;
-    const bool ldsp = G == 1 && npix <= 65535;
-    const size_t lds_par = ldsp ? (size_t)npix * 2 : 0;
-    if (ldsp && !(ctx->fz_attr_done & 1)) {
-        SPA_HIP(hipFuncSetAttribute((const void *)k_fz_pass<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-        ctx->fz_attr_done |= 1;
-    }
     // the window's root table (+ the parent array of a small image) in LDS
     const size_t lds_limit = 156 * 1024;
     const size_t par_bytes = ((size_t)npix * 2 + 15) & ~(size_t)15;
-    // (SPA_FZ_LPAR=0: experiments — small images through the large images' kernel: parent array in global memory, hub chains)
-    const bool lpar = G == 1 && npix <= 65535 && par_bytes + 2560 * 16 + FZ_THREADS * 4 <= lds_limit &&
-                      !(getenv("SPA_FZ_LPAR") && atoi(getenv("SPA_FZ_LPAR")) == 0);
+    const bool lpar = npix <= 65535 && par_bytes + 2560 * 16 + FZ_THREADS * 4 <= lds_limit;
     long long cells = lpar ? (long long)((lds_limit - par_bytes - FZ_THREADS * 4) / 16) : 4096;
     if (cells > 4096) cells = 4096;
-    // (larger images.  Round 3: the table kernel with the parent array in L2 measured 0.90 s per full-size image against 0.60 s of
-    // k_fz_pass — a round of it still chased the parent array through L2.  Round 5: the window's own merges form a forest over
-    // the table's CELLS (lcp), so a round finds its roots through LDS alone: 0.40 s against 0.52 s alone, 17.3 against 22.4 ms per
-    // image at batch 30, the same labels — the table kernel serves every image size; SPA_FZ_TAB_LARGE=0 keeps k_fz_pass)
-    const char *tab_large = getenv("SPA_FZ_TAB_LARGE");
-    const bool tab = G == 1 && !getenv("SPA_FZ_NO_LDS_STATE") && (lpar || !tab_large || atoi(tab_large) != 0);
     // (!lpar: + the hub-chain state: cells * 3 + per-edge cells / flags / costs + 16 bitmaps)
     const size_t tab_lds = lpar ? par_bytes + (size_t)cells * 16 + FZ_THREADS * 4
                                 : (size_t)cells * 22 + FZ_THREADS * 4 + (size_t)cells * 3 + FZ_THREADS * 13 + 16 + 16 * (FZ_THREADS / 32) * 4 + 16 * 4 + 16 + FZ_THREADS * 4 + FZ_THREADS * 8;
-    // hub chains (k_fz_pass_tab, !LPAR): on by default — one 1024 x 2048 image alone 0.40 -> 0.22 s (109 000 -> 8 000 full rounds),
-    // 16.9 -> 10.2 ms per image at batch 30, the same labels; SPA_FZ_HUB=0 switches them off
-    const char *hub_env = getenv("SPA_FZ_HUB");
-    const int hub_on = hub_env ? atoi(hub_env) : 7;          // bit 0: hub chains, bit 1: batched table entry, bit 2: 16-byte root records (99 against 102 ms alone)
-    if (tab && !(ctx->fz_attr_done & 2)) {
+    if (!ctx->fz_attr_done) {
         SPA_HIP(hipFuncSetAttribute((const void *)k_fz_pass_tab<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
         SPA_HIP(hipFuncSetAttribute((const void *)k_fz_pass_tab<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
-        ctx->fz_attr_done |= 2;
+        ctx->fz_attr_done = 1;
     }
-    int *diag = zcount + FZ_MAXB;              // windows, chunks, rounds of the batch (diagnostics, spa_debug_peek)
-    // large images: pass 0 in SPA_FZ_SEGMENTS launches (default 8) with a filter of the remaining sorted list between two of them, the
-    // clean-up pass behind a filter over the whole list (the filter kernels above); SPA_FZ_PREFILTER=0: one launch per pass over
-    // the sorted list itself, as round 4 ran them
-    const char *pf_env = getenv("SPA_FZ_PREFILTER");
-    const int nblk_e = (int)((g.nE + 1023) / 1024);
-    // (block counts and segment words in the radix sort's scratch — the sorts are done —, the lists in the sort's INPUT key buffer)
-    const bool prefilter = tab && !lpar && (!pf_env || atoi(pf_env) != 0) &&
-                           (size_t)B * nblk_e * 4 + (size_t)B * 32 <= tmp_bytes * (par_sort ? 3 : 1);
-    int nseg = B < 4 ? 16 : 8;             // (measured at B = 1 / 8 / 30: 116 / 158 / 255 ms with 16, 122 / 152 / 231 ms with 8)
-    if (const char *e = getenv("SPA_FZ_SEGMENTS")) nseg = atoi(e) > 0 ? atoi(e) : 1;
-    if (prefilter) {
-        int *blkcnt = (int *)tmp;
-        int *segA = blkcnt + (size_t)B * nblk_e, *segB = segA + 2 * B, *segF = segB + 2 * B;
-        unsigned *idxA = (unsigned *)keys0, *idxB = idxA + (size_t)B * g.nE;
-        int gp = (int)((npix + 255) / 256);
-        if (gp > 1024) gp = 1024;
-        const int gb = nblk_e < 2048 ? nblk_e : 2048;
-        // (hub_on bit 2: size and internal cost of a root in one 16-byte record, the table pass's only view of them)
-        const FzRec *recp = (hub_on & 4) ? (const FzRec *)cint : nullptr;
-        if (recp) hipLaunchKernelGGL(k_fz_records, dim3(2048), dim3(256), 0, s, (FzRec *)cint, (const int *)size, (long long)B * npix);
-        auto filter = [&](const unsigned *in_idx, const int *seg_in, int fmode, int *seg_out, unsigned *out_idx) {
-            hipLaunchKernelGGL(k_fz_flatten_all, dim3(gp, B), dim3(256), 0, s, parent, (int)npix);
-            hipLaunchKernelGGL(k_fz_live_count, dim3(gb, B), dim3(256), 0, s, (const unsigned *)vals1, g, (const int *)parent,
-                               (const int *)size, in_idx, seg_in, fmode, min_size, (int)npix, blkcnt, nblk_e, recp);
-            hipLaunchKernelGGL(k_fz_live_scan, dim3(B), dim3(1024), 0, s, blkcnt, nblk_e, seg_out);
-            hipLaunchKernelGGL(k_fz_live_copy, dim3(gb, B), dim3(256), 0, s, (const unsigned *)vals1, g, (const int *)parent,
-                               (const int *)size, in_idx, seg_in, fmode, min_size, (int)npix, (const int *)blkcnt, nblk_e, out_idx, recp);
-        };
-        auto pass = [&](int pmode, const unsigned *in_idx, int *seg_io, int div, int skip_flat) {
-            hipLaunchKernelGGL(k_fz_pass_tab<false>, dim3(B), dim3(FZ_THREADS), tab_lds, s,
-                               (const unsigned long long *)keys1, (const unsigned *)vals1, g, parent, size, cint, k,
-                               min_size, pmode, (const int *)zcount, flatten_every, (int)cells, diag, hub_on, in_idx, seg_io, div, skip_flat);
-        };
+    // (block counts and segment words in the radix sort's scratch, the lists in the sort's INPUT key buffer)
+    int *blkcnt = (int *)tmp;
+    int *segA = blkcnt + (size_t)B * nblk_e, *segB = segA + 2 * B, *segF = segB + 2 * B;
+    unsigned *idxA = (unsigned *)keys0, *idxB = idxA + (size_t)B * g.nE;
+    int gp = (int)((npix + 255) / 256);
+    if (gp > 1024) gp = 1024;
+    const int gb = nblk_e < 2048 ? nblk_e : 2048;
+    // large images: size and internal cost of a root in one 16-byte record, the passes' and the filters' only view of them
+    const FzRec *recp = lpar ? nullptr : (const FzRec *)cint;
+    auto filter = [&](const unsigned *in_idx, const int *seg_in, int fmode, int *seg_out, unsigned *out_idx) {
+        hipLaunchKernelGGL(k_fz_flatten_all, dim3(gp, B), dim3(256), 0, s, parent, (int)npix);
+        hipLaunchKernelGGL(k_fz_live_count, dim3(gb, B), dim3(256), 0, s, (const unsigned *)vals1, g, (const int *)parent,
+                           (const int *)size, in_idx, seg_in, fmode, min_size, (int)npix, blkcnt, nblk_e, recp);
+        hipLaunchKernelGGL(k_fz_live_scan, dim3(B), dim3(1024), 0, s, blkcnt, nblk_e, seg_out);
+        hipLaunchKernelGGL(k_fz_live_copy, dim3(gb, B), dim3(256), 0, s, (const unsigned *)vals1, g, (const int *)parent,
+                           (const int *)size, in_idx, seg_in, fmode, min_size, (int)npix, (const int *)blkcnt, nblk_e, out_idx, recp);
+    };
+    const auto pass_kernel = lpar ? k_fz_pass_tab<true> : k_fz_pass_tab<false>;
+    auto pass = [&](int pmode, const unsigned *in_idx, int *seg_io, int div, int skip_flat) {
+        hipLaunchKernelGGL(pass_kernel, dim3(B), dim3(FZ_THREADS), tab_lds, s,
+                           (const unsigned long long *)keys1, (const unsigned *)vals1, g, parent, size, cint, k,
+                           min_size, pmode, (const int *)zcount, flatten_every, (int)cells, diag, in_idx, seg_io, div, skip_flat);
+    };
+    int *sn = segA;                 // where the clean-up pass's filter writes its segment words, and its list
+    unsigned *other = idxA;
+    if (lpar) {
+        // small images (parent array in LDS): pass 0 as one launch over the sorted list itself
+        pass(0, nullptr, nullptr, 1, 0);
+    } else {
+        // large images: pass 0 in nseg launches with a filter of the remaining sorted list between two of them
+        const int nseg = B < 4 ? 16 : 8;       // (measured at B = 1 / 8 / 30: 116 / 158 / 255 ms with 16, 122 / 152 / 231 ms with 8)
+        hipLaunchKernelGGL(k_fz_records, dim3(2048), dim3(256), 0, s, (FzRec *)cint, (const int *)size, (long long)B * npix);
         hipLaunchKernelGGL(k_fz_seg_init, dim3((B + 63) / 64), dim3(64), 0, s, segA, (const int *)zcount, (int)g.nE, B);
-        hipLaunchKernelGGL(k_fz_seg_init, dim3((B + 63) / 64), dim3(64), 0, s, segF, (const int *)zcount, (int)g.nE, B);
         const unsigned *cur = nullptr;
-        int *sc = segA, *sn = segB;
-        unsigned *other = idxA;
+        int *sc = segA;
+        sn = segB;
         for (int i = 0; i < nseg; ++i) {
             pass(0, cur, sc, nseg - i, i > 0);
             if (i + 1 < nseg) {
@@ -1626,56 +1372,12 @@ static int fz_run(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t 
                 int *t = sc; sc = sn; sn = t;
             }
         }
-        filter(nullptr, segF, 1, sn, other);
-        pass(1, other, sn, 1, 1);
     }
-    // small images (parent array in LDS): pass 0 as one launch, then the same filter in front of the clean-up pass — the pass kernel
-    // wrote the parent array back, the other compute units flatten it and list the few edges that can still merge a component below
-    // min_size, and the clean-up launch walks that list instead of testing every sorted position again (SPA_FZ_PREFILTER=0: off)
-    const bool prefilter_small = tab && lpar && !prefilter && (!pf_env || atoi(pf_env) != 0) &&
-                                 (size_t)B * nblk_e * 4 + (size_t)B * 32 <= tmp_bytes * (par_sort ? 3 : 1);
-    if (prefilter_small) {
-        int *blkcnt = (int *)tmp;
-        int *segF = blkcnt + (size_t)B * nblk_e, *segL = segF + 2 * B;
-        unsigned *idxA = (unsigned *)keys0;
-        int gp = (int)((npix + 255) / 256);
-        if (gp > 1024) gp = 1024;
-        const int gb = nblk_e < 2048 ? nblk_e : 2048;
-        hipLaunchKernelGGL(k_fz_pass_tab<true>, dim3(B), dim3(FZ_THREADS), tab_lds, s,
-                           (const unsigned long long *)keys1, (const unsigned *)vals1, g, parent, size, cint, k,
-                           min_size, 0, (const int *)zcount, flatten_every, (int)cells, diag);
-        hipLaunchKernelGGL(k_fz_seg_init, dim3((B + 63) / 64), dim3(64), 0, s, segF, (const int *)zcount, (int)g.nE, B);
-        hipLaunchKernelGGL(k_fz_flatten_all, dim3(gp, B), dim3(256), 0, s, parent, (int)npix);
-        hipLaunchKernelGGL(k_fz_live_count, dim3(gb, B), dim3(256), 0, s, (const unsigned *)vals1, g, (const int *)parent,
-                           (const int *)size, (const unsigned *)nullptr, (const int *)segF, 1, min_size, (int)npix, blkcnt, nblk_e,
-                           (const FzRec *)nullptr);
-        hipLaunchKernelGGL(k_fz_live_scan, dim3(B), dim3(1024), 0, s, blkcnt, nblk_e, segL);
-        hipLaunchKernelGGL(k_fz_live_copy, dim3(gb, B), dim3(256), 0, s, (const unsigned *)vals1, g, (const int *)parent,
-                           (const int *)size, (const unsigned *)nullptr, (const int *)segF, 1, min_size, (int)npix, (const int *)blkcnt,
-                           nblk_e, idxA, (const FzRec *)nullptr);
-        hipLaunchKernelGGL(k_fz_pass_tab<true>, dim3(B), dim3(FZ_THREADS), tab_lds, s,
-                           (const unsigned long long *)keys1, (const unsigned *)vals1, g, parent, size, cint, k,
-                           min_size, 1, (const int *)zcount, flatten_every, (int)cells, diag, 0, (const unsigned *)idxA, segL, 1, 1);
-    }
-    for (int mode = 0; mode < 2 && !prefilter && !prefilter_small; ++mode) {
-        const unsigned r0 = mode ? 0x40000000u : 0u;
-        if (tab && lpar)
-            hipLaunchKernelGGL(k_fz_pass_tab<true>, dim3(B), dim3(FZ_THREADS), tab_lds, s,
-                               (const unsigned long long *)keys1, (const unsigned *)vals1, g, parent, size, cint, k,
-                               min_size, mode, (const int *)zcount, flatten_every, (int)cells, diag);
-        else if (tab)
-            hipLaunchKernelGGL(k_fz_pass_tab<false>, dim3(B), dim3(FZ_THREADS), tab_lds, s,
-                               (const unsigned long long *)keys1, (const unsigned *)vals1, g, parent, size, cint, k,
-                               min_size, mode, (const int *)zcount, flatten_every, (int)cells, diag, hub_on & 3);
-        else if (ldsp)
-            hipLaunchKernelGGL(k_fz_pass<true>, dim3(G, B), dim3(FZ_THREADS), lds_par, s, (const unsigned long long *)keys1,
-                               (const unsigned *)vals1, g, parent, size, cint, mark, st, k, min_size, mode, r0,
-                               (const int *)zcount, flatten_every, ctx->d_status);
-        else
-            hipLaunchKernelGGL(k_fz_pass<false>, dim3(G, B), dim3(FZ_THREADS), 0, s, (const unsigned long long *)keys1,
-                               (const unsigned *)vals1, g, parent, size, cint, mark, st, k, min_size, mode, r0,
-                               (const int *)zcount, flatten_every, ctx->d_status);
-    }
+    // the clean-up pass behind a filter over the whole sorted list: the pass kernel wrote the parent array back, every compute unit
+    // flattens it and lists the few edges that can still merge a component below min_size, and the clean-up launch walks that list
+    hipLaunchKernelGGL(k_fz_seg_init, dim3((B + 63) / 64), dim3(64), 0, s, segF, (const int *)zcount, (int)g.nE, B);
+    filter(nullptr, segF, 1, sn, other);
+    pass(1, other, sn, 1, 1);
     hipLaunchKernelGGL(k_fz_count_roots, dim3(nblk, B), dim3(256), 0, s, parent, (int)npix, blk, nblk);
     hipLaunchKernelGGL(k_fz_scan, dim3(B), dim3(256), 0, s, blk, nblk, n_labels);
     hipLaunchKernelGGL(k_fz_number, dim3(nblk, B), dim3(256), 0, s, parent, (int)npix, blk, nblk, rank);
@@ -1684,4 +1386,18 @@ static int fz_run(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t 
     hipLaunchKernelGGL(k_fz_relabel, dim3(gr, B), dim3(256), 0, s, parent, rank, (int)npix, labels);
     SPA_LAUNCH_CHECK();
     return SPA_OK;
+}
+
+extern "C" int spa_felzenszwalb(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t W,
+                                double scale, double sigma, int32_t min_size, int32_t *labels,
+                                int32_t *n_labels, void *stream)
+{
+    return fz_run(ctx, rgb, B, H, W, scale, sigma, min_size, labels, n_labels, stream, false);
+}
+
+extern "C" int spa_felzenszwalb_u8(spa_ctx *ctx, const float *rgb, int32_t B, int32_t H, int32_t W,
+                                   double scale, double sigma, int32_t min_size, int32_t *labels,
+                                   int32_t *n_labels, void *stream)
+{
+    return fz_run(ctx, rgb, B, H, W, scale, sigma, min_size, labels, n_labels, stream, true);
 }

@@ -62,10 +62,10 @@ def test_felzenszwalb_edge_shapes(eng, orc, synth, H, W, scale, sigma, min_size)
 
 @pytest.mark.parametrize('H,W', [(255, 257), (256, 256), (257, 256)])
 def test_felzenszwalb_lds_parent_boundary(eng, orc, synth, H, W):
-    """65 535 pixels is the last size at which the legacy k_fz_pass<true> (SPA_FZ_NO_LDS_STATE, SPA_FZ_GROUP) keeps the parent
-    array in LDS (16-bit indices, 0xFFFF = root).  The default kernel, k_fz_pass_tab, switches at 57 344 pixels — all three sizes
-    here run its global-array form; test_gpu_felzenszwalb_hostile.py brackets that switch.  Batches of three, so the sorts also
-    take the three-stream path."""
+    """65 535 pixels is the last size whose pixel indices fit the 16-bit parent entries (0xFFFF = root) that k_fz_pass_tab<true>
+    keeps in LDS.  fz_run switches to the global-array form, k_fz_pass_tab<false>, earlier — above 57 344 pixels, where the array
+    and the root table no longer fit in LDS together — so all three sizes here run that form;
+    test_gpu_felzenszwalb_hostile.py brackets the switch itself.  Batches of three, so the sorts also take the three-stream path."""
     imgs = np.stack([synth.synth_scene(300 + i, H, W, n_rect=40) for i in range(3)])
     labels, n_labels = eng.felzenszwalb(torch.from_numpy(imgs).cuda(), 120.0, 0.8, 20)
     eng.raise_on_status()
