@@ -718,6 +718,37 @@ int spa_segnet_train_classifier_backward(spa_ctx *ctx, const float *dscore, cons
 int spa_confusion(spa_ctx *ctx, const uint8_t *road, const int32_t *gt, int32_t B,
                   int64_t npix, int64_t *out, void *stream);
 
+/* ---- label PNGs (csrc/spa_png.hip) --------------------------------------------------------
+ * cv.imwrite(save_fn, mask) of utils/apply_spalign_kmeans.py:145 and utils/create_demovideo.py:64 up to the file's
+ * framing: the compressed payload of an 8-bit greyscale PNG, made on the device.  src (B,Hs,Ws) uint8, any byte
+ * values.  row_idx (Ho) and col_idx (Wo) int32 on the device: nearest-neighbour tables, every entry inside the source;
+ * the encoded image is img[b][y][x] = src[b][row_idx[y]][col_idx[x]].  NULL is the identity and requires Ho == Hs
+ * (Wo == Ws).  out + b*out_stride receives image b's RAW deflate stream (no zlib header, no Adler trailer), nbytes[b]
+ * its length and adler[b] the Adler-32 of image b's filtered scanlines; the host adds the 57 bytes of PNG framing
+ * (png.assemble).  No byte of out at or past nbytes[b] is written (the caller's buffer may hold anything).
+ *
+ * The bytes are fixed (png.deflate_rle_host restates them):
+ *   - scanline y is the byte 2 (filter type Up) followed by img[y][x] - img[y-1][x] mod 256, row -1 being zeros;
+ *   - one deflate block: the 3 header bits BFINAL = 1, BTYPE = 01 (fixed Huffman), the tokens of scanlines 0..Ho-1,
+ *     symbol 256, zero bits up to a byte;
+ *   - a scanline's Wo+1 bytes are cut into their maximal runs of equal bytes (a run never continues into the next
+ *     scanline); a run of value v and length n is the literal v, then with r = n-1, while r >= 3, a match of length
+ *     min(r, 258) at distance 1 (r reduced by it), then r more literals v;
+ *   - RFC 1951's fixed codes: Huffman codes most-significant bit first, extra bits least-significant first, the
+ *     distance code the 5 bits of code 0.
+ * spa_png_deflate_bound (host only, no context) = ceil((3 + 9*(Wo+1)*Ho + 7) / 8): a literal is at most 9 bits, a
+ * match covers at least 3 bytes with at most 18.  0 for a dimension <= 0.
+ * Refused with nothing launched: a dimension <= 0, a NULL array or identity tables with differing shapes (SPA_ERR_ARG);
+ * a bound above 2^31 - 1, the IDAT chunk's length field (SPA_ERR_ARG); out_stride below the bound (SPA_ERR_CAPACITY).
+ * Three launches on `stream` (one lane per scanline counts its bits and Adler sums; one workgroup per image scans
+ * them; one lane per scanline writes its bits): every byte of the stream has one writer, so there are no atomics and
+ * nothing is zeroed.  16-byte loads when col_idx is NULL, Ws % 16 == 0 and src is 16-byte aligned; byte loads
+ * otherwise.  No host synchronisation. */
+int spa_png_deflate_u8(spa_ctx *ctx, const uint8_t *src, int32_t B, int32_t Hs, int32_t Ws, const int32_t *row_idx,
+                       const int32_t *col_idx, int32_t Ho, int32_t Wo, uint8_t *out, int64_t out_stride,
+                       int32_t *nbytes, uint32_t *adler, void *stream);
+int64_t spa_png_deflate_bound(int32_t Ho, int32_t Wo);
+
 #ifdef __cplusplus
 }
 #endif

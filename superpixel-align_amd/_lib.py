@@ -131,6 +131,9 @@ PROTOTYPES = {
                                                  c_i32, c_p, c_p, c_p, c_p, c_p]),
     'spa_paint': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
     'spa_confusion': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i64, c_p, c_p]),
+    'spa_png_deflate_u8': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_i32, c_p, c_i64, c_p, c_p,
+                                          c_p]),
+    'spa_png_deflate_bound': (ctypes.c_int64, [c_i32, c_i32]),
     'spa_segnet_encode': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     'spa_segnet_decode': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
     'spa_segnet_encode_bf16': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p,

@@ -6,7 +6,7 @@
 Flags, defaults (including the two dead flags), the "keep the batch size" loop, the NPY /
 result.json / PNG naming and contents are the reference's; additions are optional flags
 (--arch, --dtype, --drn_weights, --pool_mode, --mean_sampling, --no_figure, --balanced, --io_threads, --decode_procs:
-ProcessDecoder below, on the slabs and workers of slabs.py).
+ProcessDecoder below, on the slabs and workers of slabs.py; the label-free driver's --png_encoder: png.py).
 Under `python -m torch.distributed.run --nproc-per-node N` the labelled driver shards the image
 range like utils/create_*_labels.sh does and rank 0 writes result.json after one all_gather.
 """
@@ -27,6 +27,7 @@ import torch  # noqa: E402
 from . import decode_worker
 from . import dist as spdist
 from . import ops
+from . import png
 from .pipeline import LabelPipeline
 from .slabs import Layout, PinnedSlabs, ShmTooSmall, Slabs, open_or_none
 
@@ -123,7 +124,10 @@ def get_args_labelfree(argv=None):
              # (the reference's default here is -1 = its NumPy path, utils/apply_spalign_kmeans.py:84; this build has no CPU path —
              # ops.create_model refuses a negative id — so the script run without --gpu takes device 0 instead of aborting)
              ('--gpu', dict(type=int, default=0)),
-             ('--out_dir', dict(type=str))]
+             ('--out_dir', dict(type=str)),
+             # pillow: the mask is downloaded, resized and deflated on the host (every byte as before); device: the PNG's
+             # compressed payload is made on the device (png.py), the host adds the framing
+             ('--png_encoder', dict(type=str, default='pillow', choices=['pillow', 'device']))]
     return _parser(extra).parse_args(argv)
 
 
@@ -369,9 +373,7 @@ def create_label_mask(label):
 
 def resize_nearest(a, shape):
     """cv.resize(..., interpolation=cv.INTER_NEAREST): src = min(floor(dst * src/dst), src-1)."""
-    h, w = shape
-    ys = np.minimum((np.arange(h) * (a.shape[0] / h)).astype(np.int64), a.shape[0] - 1)
-    xs = np.minimum((np.arange(w) * (a.shape[1] / w)).astype(np.int64), a.shape[1] - 1)
+    ys, xs = png.nearest_tables(a.shape[:2], shape)
     return a[ys][:, xs]
 
 
@@ -400,7 +402,7 @@ def score_from_counts(TN, FP, FN, TP):
 
 def nearest_index(n_dst, n_src):
     """Source index of every destination index under cv.INTER_NEAREST (see resize_nearest)."""
-    return np.minimum((np.arange(n_dst) * (n_src / n_dst)).astype(np.int64), n_src - 1)
+    return png.nearest_index(n_dst, n_src)
 
 
 def save_npy(args, img_fn, road_mask, clustering_result):
@@ -820,6 +822,11 @@ def main_labelfree(argv=None):
     from PIL import Image
     from concurrent.futures import ThreadPoolExecutor
     io_pool = ThreadPoolExecutor(max_workers=max(1, args.io_threads))
+    if args.png_encoder == 'device':
+        try:
+            return _labelfree_device_png(args, pipe, ds, img_fns, io_pool, start, end)
+        finally:
+            io_pool.shutdown()
     for lo, hi in spdist.batch_ranges(start, end, args.batchsize):
         lo = max(lo, 0)                     # see main_labelled: a range shorter than one batch
         batch = ds.batch(lo, hi, io_pool) if args.host_resize else ds.batch_device(lo, hi, io_pool, ops.engine())   # same thread
@@ -832,4 +839,67 @@ def main_labelfree(argv=None):
             save_fn = os.path.join(args.out_dir, os.path.basename(img_fns[i]))
             Image.fromarray(rm.astype(np.uint8)).save(save_fn)          # cv.imwrite(save_fn, mask)
             print(save_fn)
+    return 0
+
+
+def _labelfree_device_png(args, pipe, ds, img_fns, io_pool, start, end):
+    """main_labelfree's loop with --png_encoder device.  Per batch the road mask is encoded at --label_shape where it is
+    (png.DeviceEncoder: the nearest resize is part of the encoder's loads), on the stream that holds the result and in
+    front of everything the next batch will put there.  One batch later the host waits for that (the loop's one wait
+    per batch), the download of the used bytes goes to the encoder's side stream, and io_pool's jobs wait for it,
+    assemble the files and write them while the device labels the next batch.  The names are printed in the loop's
+    order, each once its file is written."""
+    eng = ops.engine()
+    enc = png.DeviceEncoder(eng, args.label_shape, args.batchsize)
+    written = []                            # (file name, future) of the batch whose files are being written
+
+    def drain():
+        """the files of the batch before: all written (an error is raised here), their names printed in order"""
+        for fn, job in written:
+            job.result()
+            print(fn)
+        del written[:]
+
+    def finalize(st):
+        res, slot = st['res'], st['slot']
+        st['encoded'].synchronize()         # the batch's one wait: mask, payload, lengths and status are there
+        eng.raise_on_word(st['status_h'])
+        if st['fail_h'] is not None:
+            res.check_retry(st['fail_h'])
+        elif getattr(res, 'retry_info', None) is not None:
+            res.check_retry()
+        # a re-labelled image (the last batch shifted back) must overwrite its earlier file, and the buffer set that
+        # the batch before last used is free once its writers are through
+        drain()
+        enc.fetch(slot)
+        for j, fn in enumerate(st['fns']):
+            written.append((fn, io_pool.submit(lambda j=j, fn=fn: png.write_file(fn, enc.file_bytes(slot, j)))))
+
+    prev = None
+    try:
+        for lo, hi in spdist.batch_ranges(start, end, args.batchsize):
+            lo = max(lo, 0)
+            batch = ds.batch(lo, hi, io_pool) if args.host_resize else ds.batch_device(lo, hi, io_pool, eng)
+            res = pipe.run(batch, check_status=False, join=False)
+            with torch.cuda.stream(res.stream):
+                slot = enc.encode(res.road)
+                fail_h = None
+                if res.retry_fail is not None:
+                    fail_h = torch.empty(res.retry_fail.shape, dtype=torch.bool).pin_memory()
+                    fail_h.copy_(res.retry_fail, non_blocking=True)
+                status_h = eng.status_take_async()
+                encoded = torch.cuda.Event()
+                encoded.record(res.stream)
+            st = dict(res=res, slot=slot, fns=[os.path.join(args.out_dir, os.path.basename(img_fns[i]))
+                                               for i in list(range(len(ds)))[lo:hi]],
+                      status_h=status_h, fail_h=fail_h, encoded=encoded)
+            if prev is not None:
+                finalize(prev)
+            prev = st
+        if prev is not None:
+            finalize(prev)
+        drain()
+    finally:
+        for _fn, job in written:            # after an error: what was handed over still reaches the disk
+            job.exception()
     return 0

@@ -92,6 +92,7 @@ enum {
     WS_SEGNET_WF16X3,  // SegNet split-plane training forward / dgrad and inference: the weights as two scaled f16 planes
     WS_SEGNET_AMAX,    // SegNet split-plane training and inference: per-workgroup maxima and the operands' scale exponents
     WS_SEGNET_BNRED,   // SegNet fused BatchNorm / classifier backward: per-workgroup float64 partial sums
+    WS_PNG_ROWS,       // label PNG encoder: per scanline the bit count, then the bit offset, and two Adler-32 partial sums
     WS_COUNT
 };
 

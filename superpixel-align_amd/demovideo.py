@@ -10,7 +10,8 @@ their argmax: SegNetBasic.predict_labels), and one launch makes the mask -- Engi
 Engine.segnet_overlay, which blends the road colour into the frames that are on the device already.  Masks and blended
 frames come back into one of two pinned buffer sets, and the host writes batch k-1's files while batch k is on the
 device.  With loader_procs > 0 the frames are decoded by worker processes into pinned shared-memory slabs (slabs.Ring,
-decode_worker.png_into), a few batches ahead.
+decode_worker.png_into), a few batches ahead.  With png_encoder='device' (--png_encoder device) the mask is not
+downloaded: png.DeviceEncoder makes the PNG's compressed payload from it on the device and only those bytes come back.
 
 blend_host is create_movie.py's numpy statement, MjpegAviWriter a plain RIFF AVI of Pillow-encoded JPEG frames, and
 write_movie the reference's second script on them.  What is pinned: the labels (the argmax of Pillow's BILINEAR resize
@@ -28,6 +29,7 @@ import time
 import numpy as np
 
 from . import decode_worker
+from . import png
 from .slabs import DeviceSlabStage, Layout, Ring, open_or_none
 
 ROAD_COLOR = (128, 64, 128)          # create_movie.py:23 (symmetric: the same in OpenCV's BGR and in RGB)
@@ -242,7 +244,8 @@ class FrameLoader(Ring):
 
 
 def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=(1024, 2048), batchsize=4,
-                 loader_procs=0, video=None, encode_threads=4, color=ROAD_COLOR, alpha=ALPHA, stats=None):
+                 loader_procs=0, video=None, encode_threads=4, color=ROAD_COLOR, alpha=ALPHA, stats=None,
+                 png_encoder='pillow'):
     """create_demovideo.py:57-64 over frame_fns with model (a segnet.SegNetBasic): <out_dir>/<basename(frame)> = the
     label of SegNetBasic.predict_labels for the frame resized to input_shape (an 8-bit single-channel PNG of 0 / 1 at
     pred_shape), and with video (an MjpegAviWriter of size (pred W, pred H)) create_movie.py's frame appended to it, the
@@ -250,7 +253,9 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
     frames ahead; the outputs are the same, byte for byte.  encode_threads: threads that write the PNGs.  With video a
     frame whose size is not pred_shape is refused (ValueError) before any file is written.  stats: a dict that
     receives loop_s, n_batches, n_host_batches and the seconds spent waiting for the loader (loader_wait_s), waiting for
-    the device (device_wait_s) and writing (output_s).  -> the number of frames."""
+    the device (device_wait_s) and writing (output_s).  png_encoder 'device': the PNG's compressed payload is made
+    on the device from the mask where it is (png.DeviceEncoder; the same pixels in another stream), the mask itself is
+    not downloaded, and with a stats dict png_payload_bytes counts what was.  -> the number of frames."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     clock = time.perf_counter
@@ -259,6 +264,9 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
     input_shape = tuple(int(v) for v in input_shape)
     pred_shape = tuple(int(v) for v in pred_shape)
     B = max(int(batchsize), 1)
+    if png_encoder not in ('pillow', 'device'):
+        raise ValueError('label_frames: png_encoder must be pillow or device, got %r' % (png_encoder,))
+    enc = png.DeviceEncoder(eng, pred_shape, B) if png_encoder == 'device' else None
     first = None
     if video is not None:
         if (video.height, video.width) != pred_shape:
@@ -273,7 +281,7 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
     if not os.path.exists(out_dir):
         os.makedirs(out_dir, exist_ok=True)
 
-    ring = [{'mask': torch.empty((B,) + pred_shape, dtype=torch.uint8).pin_memory(),
+    ring = [{'mask': torch.empty((B,) + pred_shape, dtype=torch.uint8).pin_memory() if enc is None else None,
              'blended': torch.empty((B,) + pred_shape + (3,), dtype=torch.uint8).pin_memory() if video is not None
              else None} for _ in range(2)]
     times = {'loader_wait_s': 0.0, 'device_wait_s': 0.0, 'output_s': 0.0}
@@ -287,9 +295,16 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
         t0 = clock()
         rec['event'].synchronize()
         t1 = clock()
-        mask_h = rec['buf']['mask'].numpy()
-        jobs = [png_pool.submit(write_label_png, os.path.join(out_dir, os.path.basename(fn)), mask_h[j])
-                for j, fn in enumerate(rec['fns'])]
+        if enc is None:
+            mask_h = rec['buf']['mask'].numpy()
+            jobs = [png_pool.submit(write_label_png, os.path.join(out_dir, os.path.basename(fn)), mask_h[j])
+                    for j, fn in enumerate(rec['fns'])]
+        else:
+            # the lengths are here: only the used bytes come down, on the encoder's stream; the writers wait for them
+            enc.fetch(rec['slot'])
+            jobs = [png_pool.submit(lambda j=j, fn=fn: png.write_file(os.path.join(out_dir, os.path.basename(fn)),
+                                                                      enc.file_bytes(rec['slot'], j)))
+                    for j, fn in enumerate(rec['fns'])]
         if video is not None:
             blended_h = rec['buf']['blended'].numpy()
             for j in range(len(rec['fns'])):
@@ -312,11 +327,15 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
             buf['blended'][:n].copy_(blended, non_blocking=True)
         else:
             mask, _ = eng.segnet_score(z, pred_shape)
-        buf['mask'][:n].copy_(mask, non_blocking=True)
+        slot = None
+        if enc is None:
+            buf['mask'][:n].copy_(mask, non_blocking=True)
+        else:
+            slot = enc.encode(mask)
         event = torch.cuda.Event()
         event.record()
         flush()
-        pending[0] = {'fns': fns, 'buf': buf, 'event': event}
+        pending[0] = {'fns': fns, 'buf': buf, 'event': event, 'slot': slot}
 
     def host_batch(fns):
         """decoded here; frames of one size that follow each other share a chain"""
@@ -357,6 +376,8 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
         png_pool.shutdown(wait=True)
     if stats is not None:
         stats.update(times, loop_s=clock() - t_loop, n_batches=count[0], n_host_batches=count[1])
+        if enc is not None:
+            stats['png_payload_bytes'] = enc.downloaded
     return len(frame_fns)
 
 
@@ -387,6 +408,8 @@ def demovideo_parser():
     parser.add_argument('--out_video_fn', type=str, default=None,
                         help='also write create_movie.py\'s video, in the same pass')
     parser.add_argument('--encode_threads', type=int, default=4)
+    parser.add_argument('--png_encoder', type=str, default='pillow', choices=['pillow', 'device'],
+                        help='device: the label PNGs\' compressed payload is made on the device (the same pixels)')
     return parser
 
 
@@ -407,7 +430,8 @@ def demovideo_main(argv=None):
                                encode_threads=args.encode_threads)
     try:
         return label_frames(model, demo_frames(args.demoVideo_dir), args.out_dir, args.input_shape, args.eval_shape,
-                            args.batchsize, args.loader_procs, video, args.encode_threads)
+                            args.batchsize, args.loader_procs, video, args.encode_threads,
+                            png_encoder=args.png_encoder)
     finally:
         if video is not None:
             video.close()

@@ -1275,6 +1275,54 @@ class Engine(object):
                                       self._s()))
         return out
 
+    # ---- label PNGs (png.py)
+    def png_deflate(self, src, out_shape=None, out=None, nbytes=None, adler=None):
+        """src (B,Hs,Ws) uint8 -> (out (B,stride) uint8, nbytes (B) int32, adler (B) int32), all on the device: row b of
+        out begins with the raw deflate stream of image b's label PNG (nbytes[b] bytes; nothing at or past them is
+        written) and adler[b] holds the bits of the Adler-32 of its filtered scanlines; png.assemble makes the file.
+        out_shape (Ho, Wo): the image is first resized as cv.INTER_NEAREST does it (png.nearest_tables), inside the
+        encoder's loads.  out / nbytes / adler: the caller's buffers (stride >= spa_png_deflate_bound(Ho, Wo));
+        without them the engine's own, which the next call without them overwrites."""
+        from . import png
+        src = _req(src, torch.uint8, 'src')
+        if src.dim() != 3:
+            raise SpalignError('png_deflate: src must be (B,Hs,Ws) uint8, got %s' % (tuple(src.shape),))
+        B, Hs, Ws = (int(v) for v in src.shape)
+        Ho, Wo = (Hs, Ws) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+        rows = cols = None
+        if (Ho, Wo) != (Hs, Ws):
+            key = ('png', Hs, Ws, Ho, Wo)
+            if key not in self._in_tables:
+                if min(Hs, Ws, Ho, Wo) <= 0:
+                    raise SpalignError('png_deflate: %s -> %s' % ((Hs, Ws), (Ho, Wo)))
+                self._in_tables[key] = tuple(torch.from_numpy(t.astype(np.int32)).to(self.device)
+                                             for t in png.nearest_tables((Hs, Ws), (Ho, Wo)))
+            rows, cols = self._in_tables[key]
+        if out is None:
+            stride = (int(self._lib.spa_png_deflate_bound(Ho, Wo)) + 15) // 16 * 16
+            own = getattr(self, '_png_out', None)
+            if own is None or own.shape[0] < B or own.shape[1] < stride:
+                own = self._png_out = torch.empty((B, max(stride, 16)), dtype=torch.uint8, device=self.device)
+            out = own[:B]
+        if nbytes is None or adler is None:
+            own = getattr(self, '_png_meta', None)
+            if own is None or own.shape[1] < B:
+                own = self._png_meta = torch.empty((2, B), dtype=torch.int32, device=self.device)
+            nbytes = own[0, :B] if nbytes is None else nbytes
+            adler = own[1, :B] if adler is None else adler
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1):
+            raise SpalignError('png_deflate: out must be a (B,stride) uint8 CUDA tensor with contiguous rows')
+        if out.shape[1] < int(self._lib.spa_png_deflate_bound(Ho, Wo)):
+            raise SpalignError('png_deflate: a row of out holds %d bytes, spa_png_deflate_bound(%d, %d) is %d'
+                               % (out.shape[1], Ho, Wo, int(self._lib.spa_png_deflate_bound(Ho, Wo))))
+        for t, what in ((nbytes, 'nbytes'), (adler, 'adler')):
+            if tuple(_req(t, torch.int32, what).shape) != (B,):
+                raise SpalignError('png_deflate: %s must be (%d,) int32' % (what, B))
+        check(self._lib.spa_png_deflate_u8(self._ctx, _ptr(src), B, Hs, Ws, _ptr(rows), _ptr(cols), Ho, Wo, _ptr(out),
+                                           int(out.stride(0)) if B > 1 else int(out.shape[1]), _ptr(nbytes),
+                                           _ptr(adler), self._s()))
+        return out, nbytes, adler
+
 
 _DEFAULT = None
 
