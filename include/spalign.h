@@ -749,6 +749,52 @@ int spa_png_deflate_u8(spa_ctx *ctx, const uint8_t *src, int32_t B, int32_t Hs, 
                        int32_t *nbytes, uint32_t *adler, void *stream);
 int64_t spa_png_deflate_bound(int32_t Ho, int32_t Wo);
 
+/* ---- JPEG frames of the demo movie (csrc/spa_jpeg.hip) -------------------------------------
+ * The entropy-coded scan of a baseline sequential JFIF frame, made on the device: 8-bit, YCbCr 4:2:0 (luminance 2x2,
+ * chrominance 1x1), Pillow's tables at quality 75, restart intervals of Ri MCUs (an MCU is 16x16 pixels).  rgb
+ * (B,H,W,3) uint8, H and W multiples of 16.  out + b*out_stride receives frame b's scan -- the intervals' bytes and
+ * the RST markers between them, in order -- and nbytes[b] its length; the host adds the segments before it and EOI
+ * (jpeg.assemble).  No byte of out at or past nbytes[b] is written.  coef_ws: B * (H/16) * (W/16) * 384 int16 on the
+ * device, 16-byte aligned; it holds the quantised coefficients between the kernels (768 bytes per MCU: the blocks
+ * Y00 Y01 Y10 Y11 Cb Cr, each in zigzag order).
+ *
+ * The bytes are fixed (jpeg.encode_host restates them); they are not libjpeg's.
+ *   - colour, arithmetic shifts:  Y  = ( 19595 R + 38470 G +  7471 B +   32768) >> 16
+ *                                 Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16
+ *                                 Cr = ( 32768 R - 27439 G -  5329 B + 8421375) >> 16
+ *   - a chrominance sample is (a + b + c + d + 2) >> 2 of its 2x2 pixels' Cb (Cr);
+ *   - the DCT of s = sample - 128 in int32, T = SPA_JPEG_DCT below (T[u][x] = round(8192 * 1/2 * c(u) *
+ *     cos((2x+1) u pi / 16)), c(0) = 1/sqrt 2):  a[y][u] = (sum_x T[u][x] s[y][x] + 1024) >> 11, then
+ *     b[v][u] = sum_y T[v][y] a[y][u]; |a| <= 1449 and |b| < 2^26;
+ *   - q = sign(b) * ((|b| + d/2) div d), d = Q[v][u] << 15, Q the quality-75 luminance table for Y and the
+ *     chrominance table for Cb and Cr;
+ *   - standard baseline entropy coding with the standard Huffman tables: MCUs in raster order, the blocks of an MCU
+ *     in the order above, DC as the difference from the component's predictor, AC in zigzag order with ZRL for runs
+ *     above 15 and EOB unless coefficient 63 is non-zero, bits most-significant first;
+ *   - interval k covers the MCUs [k Ri, min((k+1) Ri, nMCU)), starts from predictors 0, is padded to a byte with
+ *     1-bits, has a 0x00 after each of its 0xFF bytes (the padded one included), and is followed by FF D0+(k mod 8)
+ *     unless it is the last.  An Ri above nMCU is one interval.
+ * spa_jpeg_scan_bound (host only, no context) = 2 * SPA_JPEG_MCU_BYTES_MAX * nMCU + 2 * (nInt - 1).  A block is at most
+ * (11 + 11) + 63 * (16 + 10) = 1660 bits: the longest DC code and the largest baseline DC category, then 63
+ * coefficients of a 16-bit code and 10 bits each; six blocks are 1245 bytes exactly.  An interval of n MCUs is
+ * therefore at most 1245 n bytes, its padding included (padding completes a byte that the count already holds);
+ * every byte may be 0xFF and stuffed, which doubles it; and every interval but the last ends in a 2-byte marker.
+ * 0 for arguments that are refused.
+ * Refused with SPA_ERR_ARG and nothing launched: a NULL pointer, B <= 0, H or W not a positive multiple of 16, Ri < 1,
+ * coef_ws not 16-byte aligned, a bound above 2^31 - 1, out_stride below the bound.
+ * Four launches (one wave per MCU transforms; one lane per interval counts its bytes; one workgroup per image scans
+ * them; one lane per interval writes): intervals end on bytes, so every byte has one writer: no atomics, nothing is
+ * zeroed, the same bits on every call.  No host synchronisation. */
+#define SPA_JPEG_MCU_BYTES_MAX 1245
+#define SPA_JPEG_DCT                                                                                       \
+    {{2896, 2896, 2896, 2896, 2896, 2896, 2896, 2896}, {4017, 3406, 2276, 799, -799, -2276, -3406, -4017}, \
+     {3784, 1567, -1567, -3784, -3784, -1567, 1567, 3784}, {3406, -799, -4017, -2276, 2276, 4017, 799, -3406}, \
+     {2896, -2896, -2896, 2896, 2896, -2896, -2896, 2896}, {2276, -4017, 799, 3406, -3406, -799, 4017, -2276}, \
+     {1567, -3784, 3784, -1567, -1567, 3784, -3784, 1567}, {799, -2276, 3406, -4017, 4017, -3406, 2276, -799}}
+int spa_jpeg_encode_rgb8(spa_ctx *ctx, const uint8_t *rgb, int32_t B, int32_t H, int32_t W, int32_t Ri,
+                         int16_t *coef_ws, uint8_t *out, int64_t out_stride, int32_t *nbytes, void *stream);
+int64_t spa_jpeg_scan_bound(int32_t H, int32_t W, int32_t Ri);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,7 @@ enum {
     WS_SEGNET_AMAX,    // SegNet split-plane training and inference: per-workgroup maxima and the operands' scale exponents
     WS_SEGNET_BNRED,   // SegNet fused BatchNorm / classifier backward: per-workgroup float64 partial sums
     WS_PNG_ROWS,       // label PNG encoder: per scanline the bit count, then the bit offset, and two Adler-32 partial sums
+    WS_JPEG_INTERVALS, // JPEG frame encoder: per restart interval the byte count, then the byte offset in its frame
     WS_COUNT
 };
 

@@ -12,6 +12,9 @@ frames come back into one of two pinned buffer sets, and the host writes batch k
 device.  With loader_procs > 0 the frames are decoded by worker processes into pinned shared-memory slabs (slabs.Ring,
 decode_worker.png_into), a few batches ahead.  With png_encoder='device' (--png_encoder device) the mask is not
 downloaded: png.DeviceEncoder makes the PNG's compressed payload from it on the device and only those bytes come back.
+With jpeg_encoder='device' (--jpeg_encoder device) and a video the blended frames are not downloaded either:
+jpeg.DeviceEncoder makes each frame's entropy-coded scan on the device (this project's baseline JPEG at quality 75, not
+Pillow's bytes), and the writer threads frame the scans that come back.
 
 blend_host is create_movie.py's numpy statement, MjpegAviWriter a plain RIFF AVI of Pillow-encoded JPEG frames, and
 write_movie the reference's second script on them.  What is pinned: the labels (the argmax of Pillow's BILINEAR resize
@@ -29,6 +32,7 @@ import time
 import numpy as np
 
 from . import decode_worker
+from . import jpeg
 from . import png
 from .slabs import DeviceSlabStage, Layout, Ring, open_or_none
 
@@ -82,7 +86,8 @@ class MjpegAviWriter(object):
     then idx1 (offsets from the 'movi' tag).  size = (width, height) as OpenCV takes it; write() takes (height, width,
     3) uint8 RGB frames and raises on another shape (OpenCV drops such a frame silently).  Frames are JPEG-encoded with
     Pillow in encode_threads threads and stored in the order of the write() calls; write() copies nothing, so the frame
-    must stay as it is until flush() or close() returns.  The counts and sizes are patched in by close().  Raises
+    must stay as it is until flush() or close() returns.  write_encoded() stores the bytes of a ready JPEG file as the
+    next frame, after every frame given to write() before it.  The counts and sizes are patched in by close().  Raises
     ValueError before a chunk would take the file past what 32-bit RIFF sizes hold (riff_limit)."""
     HEADER_BYTES = 224               # everything before the first chunk
 
@@ -133,6 +138,17 @@ class MjpegAviWriter(object):
         self.pending.append(self.pool.submit(encode_jpeg, frame, self.quality))
         while len(self.pending) > self.depth:
             self._store(self.pending.popleft().result())
+
+    def write_encoded(self, data):
+        """the next frame is `data`, a whole JPEG file (SOI ... EOI) of the writer's frame size; the caller answers for
+        the size.  Frames still being encoded for write() are stored first."""
+        if self.fp is None:
+            raise ValueError('MjpegAviWriter: the file is closed')
+        if not (isinstance(data, (bytes, bytearray)) and len(data) >= 4 and bytes(data[:2]) == b'\xff\xd8'
+                and bytes(data[-2:]) == b'\xff\xd9'):
+            raise ValueError('MjpegAviWriter: write_encoded takes the bytes of a JPEG file, SOI to EOI')
+        self.flush()
+        self._store(bytes(data))
 
     def _store(self, data):
         padded = len(data) + (len(data) & 1)
@@ -245,7 +261,7 @@ class FrameLoader(Ring):
 
 def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=(1024, 2048), batchsize=4,
                  loader_procs=0, video=None, encode_threads=4, color=ROAD_COLOR, alpha=ALPHA, stats=None,
-                 png_encoder='pillow'):
+                 png_encoder='pillow', jpeg_encoder='pillow', jpeg_restart=None):
     """create_demovideo.py:57-64 over frame_fns with model (a segnet.SegNetBasic): <out_dir>/<basename(frame)> = the
     label of SegNetBasic.predict_labels for the frame resized to input_shape (an 8-bit single-channel PNG of 0 / 1 at
     pred_shape), and with video (an MjpegAviWriter of size (pred W, pred H)) create_movie.py's frame appended to it, the
@@ -255,7 +271,11 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
     receives loop_s, n_batches, n_host_batches and the seconds spent waiting for the loader (loader_wait_s), waiting for
     the device (device_wait_s) and writing (output_s).  png_encoder 'device': the PNG's compressed payload is made
     on the device from the mask where it is (png.DeviceEncoder; the same pixels in another stream), the mask itself is
-    not downloaded, and with a stats dict png_payload_bytes counts what was.  -> the number of frames."""
+    not downloaded, and with a stats dict png_payload_bytes counts what was.  jpeg_encoder 'device' (with video only;
+    pred_shape a multiple of 16): the blended frames stay on the device, jpeg.DeviceEncoder makes their scans there in
+    restart intervals of jpeg_restart MCUs (jpeg.DEFAULT_RI), only the scans come back, the writer threads make them
+    files (jpeg.assemble) and the video takes them in order (write_encoded); the pinned blended ring is not
+    allocated, and with a stats dict jpeg_payload_bytes counts what was downloaded.  -> the number of frames."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     clock = time.perf_counter
@@ -266,7 +286,12 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
     B = max(int(batchsize), 1)
     if png_encoder not in ('pillow', 'device'):
         raise ValueError('label_frames: png_encoder must be pillow or device, got %r' % (png_encoder,))
+    if jpeg_encoder not in ('pillow', 'device'):
+        raise ValueError('label_frames: jpeg_encoder must be pillow or device, got %r' % (jpeg_encoder,))
     enc = png.DeviceEncoder(eng, pred_shape, B) if png_encoder == 'device' else None
+    jenc = None
+    if jpeg_encoder == 'device' and video is not None:
+        jenc = jpeg.DeviceEncoder(eng, pred_shape, B, jpeg.DEFAULT_RI if jpeg_restart is None else jpeg_restart)
     first = None
     if video is not None:
         if (video.height, video.width) != pred_shape:
@@ -282,8 +307,8 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
         os.makedirs(out_dir, exist_ok=True)
 
     ring = [{'mask': torch.empty((B,) + pred_shape, dtype=torch.uint8).pin_memory() if enc is None else None,
-             'blended': torch.empty((B,) + pred_shape + (3,), dtype=torch.uint8).pin_memory() if video is not None
-             else None} for _ in range(2)]
+             'blended': torch.empty((B,) + pred_shape + (3,), dtype=torch.uint8).pin_memory()
+             if video is not None and jenc is None else None} for _ in range(2)]
     times = {'loader_wait_s': 0.0, 'device_wait_s': 0.0, 'output_s': 0.0}
     pending, count = [None], [0, 0]
     png_pool = ThreadPoolExecutor(max_workers=max(int(encode_threads), 1))
@@ -305,7 +330,13 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
             jobs = [png_pool.submit(lambda j=j, fn=fn: png.write_file(os.path.join(out_dir, os.path.basename(fn)),
                                                                       enc.file_bytes(rec['slot'], j)))
                     for j, fn in enumerate(rec['fns'])]
-        if video is not None:
+        if jenc is not None:
+            # as for the PNGs: the scans' used bytes come down on the encoder's stream, the writers frame them
+            jenc.fetch(rec['jslot'])
+            files = [png_pool.submit(jenc.file_bytes, rec['jslot'], j) for j in range(len(rec['fns']))]
+            for job in files:
+                video.write_encoded(job.result())
+        elif video is not None:
             blended_h = rec['buf']['blended'].numpy()
             for j in range(len(rec['fns'])):
                 video.write(blended_h[j])
@@ -322,12 +353,15 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
         z = model.forward(x, logits=True)
         buf = ring[count[0] % 2]
         count[0] += 1
+        slot = jslot = None
         if video is not None:
             mask, blended = eng.segnet_overlay(z, frames, color, alpha)
-            buf['blended'][:n].copy_(blended, non_blocking=True)
+            if jenc is None:
+                buf['blended'][:n].copy_(blended, non_blocking=True)
+            else:
+                jslot = jenc.encode(blended)
         else:
             mask, _ = eng.segnet_score(z, pred_shape)
-        slot = None
         if enc is None:
             buf['mask'][:n].copy_(mask, non_blocking=True)
         else:
@@ -335,7 +369,7 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
         event = torch.cuda.Event()
         event.record()
         flush()
-        pending[0] = {'fns': fns, 'buf': buf, 'event': event, 'slot': slot}
+        pending[0] = {'fns': fns, 'buf': buf, 'event': event, 'slot': slot, 'jslot': jslot}
 
     def host_batch(fns):
         """decoded here; frames of one size that follow each other share a chain"""
@@ -378,6 +412,8 @@ def label_frames(model, frame_fns, out_dir, input_shape=(512, 1024), pred_shape=
         stats.update(times, loop_s=clock() - t_loop, n_batches=count[0], n_host_batches=count[1])
         if enc is not None:
             stats['png_payload_bytes'] = enc.downloaded
+        if jenc is not None:
+            stats['jpeg_payload_bytes'] = jenc.downloaded
     return len(frame_fns)
 
 
@@ -410,6 +446,10 @@ def demovideo_parser():
     parser.add_argument('--encode_threads', type=int, default=4)
     parser.add_argument('--png_encoder', type=str, default='pillow', choices=['pillow', 'device'],
                         help='device: the label PNGs\' compressed payload is made on the device (the same pixels)')
+    parser.add_argument('--jpeg_encoder', type=str, default='pillow', choices=['pillow', 'device'],
+                        help='device: with --out_video_fn the video\'s JPEG frames are encoded on the device (baseline '
+                             'JPEG at quality 75 with restart markers; not Pillow\'s bytes); --eval_shape must be '
+                             'multiples of 16')
     return parser
 
 
@@ -420,6 +460,9 @@ def demovideo_main(argv=None):
     args = parser.parse_args(argv)
     if args.split_planes and args.dtype != 'fp32':
         parser.error('--split_planes is the float32-accurate mode: it cannot be combined with --dtype %s' % args.dtype)
+    if args.jpeg_encoder == 'device' and args.out_video_fn and (args.eval_shape[0] % 16 or args.eval_shape[1] % 16):
+        parser.error('--jpeg_encoder device encodes frames whose sides are multiples of 16, not --eval_shape %d %d'
+                     % tuple(args.eval_shape))
     device = max(int(args.gpu), 0)                       # -1, the reference's CPU mode: device 0 (there is no CPU path)
     torch.cuda.set_device(device)
     model = segnet.SegNetBasic.from_snapshot_file(args.snapshot, pred_shape=args.eval_shape, device=device,
@@ -431,7 +474,7 @@ def demovideo_main(argv=None):
     try:
         return label_frames(model, demo_frames(args.demoVideo_dir), args.out_dir, args.input_shape, args.eval_shape,
                             args.batchsize, args.loader_procs, video, args.encode_threads,
-                            png_encoder=args.png_encoder)
+                            png_encoder=args.png_encoder, jpeg_encoder=args.jpeg_encoder)
     finally:
         if video is not None:
             video.close()

@@ -1323,6 +1323,54 @@ class Engine(object):
                                            _ptr(adler), self._s()))
         return out, nbytes, adler
 
+    # ---- JPEG frames (jpeg.py)
+    def jpeg_encode(self, rgb, Ri=None, out=None, nbytes=None, coef=None):
+        """rgb (B,H,W,3) uint8, H and W multiples of 16 -> (out (B,stride) uint8, nbytes (B) int32) on the device: row
+        b of out begins with the entropy-coded scan of frame b's JPEG in restart intervals of Ri MCUs (nbytes[b]
+        bytes; nothing at or past them is written); jpeg.assemble makes the file.  out / nbytes / coef: the caller's
+        buffers (stride >= spa_jpeg_scan_bound(H, W, Ri); coef at least B * H * W * 3 / 2 int16, the workspace of the
+        quantised coefficients); without them the engine's own, which the next call without them overwrites."""
+        from . import jpeg
+        rgb = _req(rgb, torch.uint8, 'rgb')
+        if rgb.dim() != 4 or rgb.shape[3] != 3:
+            raise SpalignError('jpeg_encode: rgb must be (B,H,W,3) uint8, got %s' % (tuple(rgb.shape),))
+        B, H, W = (int(v) for v in rgb.shape[:3])
+        Ri = jpeg.DEFAULT_RI if Ri is None else int(Ri)
+        bound = int(self._lib.spa_jpeg_scan_bound(H, W, Ri))
+        if B <= 0 or bound <= 0:
+            raise SpalignError('jpeg_encode: %d frames of %d x %d (multiples of 16) with a restart interval of %d MCUs'
+                               % (B, H, W, Ri))
+        if out is None:
+            stride = (bound + 15) // 16 * 16
+            own = getattr(self, '_jpeg_out', None)
+            if own is None or own.shape[0] < B or own.shape[1] < stride:
+                own = self._jpeg_out = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
+            out = own[:B]
+        if nbytes is None:
+            own = getattr(self, '_jpeg_meta', None)
+            if own is None or own.shape[0] < B:
+                own = self._jpeg_meta = torch.empty((B,), dtype=torch.int32, device=self.device)
+            nbytes = own[:B]
+        n_coef = B * H * W * 3 // 2
+        if coef is None:
+            own = getattr(self, '_jpeg_coef', None)
+            if own is None or own.numel() < n_coef:
+                own = self._jpeg_coef = torch.empty((n_coef,), dtype=torch.int16, device=self.device)
+            coef = own
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1):
+            raise SpalignError('jpeg_encode: out must be a (B,stride) uint8 CUDA tensor with contiguous rows')
+        if out.shape[1] < bound:
+            raise SpalignError('jpeg_encode: a row of out holds %d bytes, spa_jpeg_scan_bound(%d, %d, %d) is %d'
+                               % (out.shape[1], H, W, Ri, bound))
+        if tuple(_req(nbytes, torch.int32, 'nbytes').shape) != (B,):
+            raise SpalignError('jpeg_encode: nbytes must be (%d,) int32' % B)
+        if _req(coef, torch.int16, 'coef').numel() < n_coef:
+            raise SpalignError('jpeg_encode: coef must hold %d int16' % n_coef)
+        check(self._lib.spa_jpeg_encode_rgb8(self._ctx, _ptr(rgb), B, H, W, Ri, _ptr(coef), _ptr(out),
+                                             int(out.stride(0)) if B > 1 else int(out.shape[1]), _ptr(nbytes),
+                                             self._s()))
+        return out, nbytes
+
 
 _DEFAULT = None
 
