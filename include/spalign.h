@@ -795,6 +795,43 @@ int spa_jpeg_encode_rgb8(spa_ctx *ctx, const uint8_t *rgb, int32_t B, int32_t H,
                          int16_t *coef_ws, uint8_t *out, int64_t out_stride, int32_t *nbytes, void *stream);
 int64_t spa_jpeg_scan_bound(int32_t H, int32_t W, int32_t Ri);
 
+/* ---- overview figures of the drivers (csrc/spa_figure.hip) ---------------------------------
+ * The per-image overview figure (batch_spalign_kmeans.py:361-386, labels_from_segnet.py) composed where its sources
+ * are: P panels, 1 <= P <= SPA_FIGURE_MAX_PANELS, in a layout of R rows x C columns (R * C >= P), each a decimated
+ * view of one index plane coloured through a table, alone or blended over the frame.  frames (B,H,W,3) uint8 or NULL;
+ * planes[p] (B,H,W) uint8 and luts[p] (256,3) uint8 on the device (the arrays planes, luts and modes themselves are P
+ * entries on the host; planes may alias one another, nothing is written through them); modes[p] SPA_FIGURE_TABLE (the
+ * table's colour) or SPA_FIGURE_BLEND (the table's colour at 0.4 over the frame: matplotlib's alpha=0.4 overlay, done
+ * exactly).  out: the canvas (B,Hc,Wc,3) uint8.
+ *
+ * The bytes are fixed (figure.compose_host restates them); they are not matplotlib's.  Integers only:
+ *   - Hp = ceil(H / d), Wp = ceil(W / d), 1 <= d <= SPA_FIGURE_MAX_DECIMATE; 0 <= g <= SPA_FIGURE_MAX_GAP;
+ *     Hc = R * Hp + (R + 1) * g rounded up to a multiple of 16 and Wc likewise from C and Wp (what
+ *     spa_jpeg_encode_rgb8 takes).  spa_figure_canvas_shape (host only, no context) stores them and returns SPA_OK, or
+ *     SPA_ERR_ARG for arguments that the composer refuses;
+ *   - panel p occupies the canvas rows g + (p div C) * (Hp + g) + [0, Hp) and columns g + (p mod C) * (Wp + g) + [0, Wp);
+ *   - panel pixel (y, x) covers the source rows [y d, min((y + 1) d, H)) and columns [x d, min((x + 1) d, W)): n pixels;
+ *   - per channel c, with L = luts[p][planes[p][pixel]][c] and v = frames[pixel][c]:  t = 5 L (SPA_FIGURE_TABLE),
+ *     t = 3 v + 2 L (SPA_FIGURE_BLEND);  S = the sum of t over the window;  out = (2 S + 5 n) div (10 n): the mean of
+ *     t / 5 rounded half up (S <= 256 * 1275, so everything fits 32 bits);
+ *   - every other canvas byte (the gaps, the padding up to the multiple of 16, the cells past panel P - 1) is 255.
+ * Refused with SPA_ERR_ARG and nothing launched: a NULL ctx, planes, luts, modes, out, plane or table; B, H or W <= 0; P
+ * outside 1..4; R or C < 1 or R * C < P; d or g out of range; a mode other than the two; a SPA_FIGURE_BLEND panel with
+ * frames NULL; Hc or Wc different from spa_figure_canvas_shape's.
+ * One launch: a lane per 16 source columns of one panel row (16-byte loads of the plane and the frame) when d divides
+ * 16, W % 16 == 0 and frames and every plane are 16-byte aligned, a lane per panel pixel with byte loads otherwise; the
+ * launch's remaining workgroups fill what no panel covers.  Every canvas byte is written exactly once: no atomics,
+ * nothing is zeroed, the same bits on every call.  No host synchronisation. */
+#define SPA_FIGURE_MAX_PANELS 4
+#define SPA_FIGURE_MAX_DECIMATE 16
+#define SPA_FIGURE_MAX_GAP 64
+#define SPA_FIGURE_TABLE 0
+#define SPA_FIGURE_BLEND 1
+int spa_figure_compose_u8(spa_ctx *ctx, const uint8_t *frames, int32_t B, int32_t H, int32_t W, int32_t P,
+                          const uint8_t *const *planes, const uint8_t *const *luts, const int32_t *modes, int32_t R,
+                          int32_t C, int32_t d, int32_t g, uint8_t *out, int32_t Hc, int32_t Wc, void *stream);
+int spa_figure_canvas_shape(int32_t H, int32_t W, int32_t R, int32_t C, int32_t d, int32_t g, int32_t *Hc, int32_t *Wc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,10 @@ PROTOTYPES = {
     'spa_png_deflate_bound': (ctypes.c_int64, [c_i32, c_i32]),
     'spa_jpeg_encode_rgb8': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_i64, c_p, c_p]),
     'spa_jpeg_scan_bound': (ctypes.c_int64, [c_i32, c_i32, c_i32]),
+    'spa_figure_compose_u8': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32,
+                                             c_p, c_i32, c_i32, c_p]),
+    'spa_figure_canvas_shape': (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32),
+                                               ctypes.POINTER(c_i32)]),
     'spa_segnet_encode': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     'spa_segnet_decode': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
     'spa_segnet_encode_bf16': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p,

@@ -6,7 +6,8 @@
 Flags, defaults (including the two dead flags), the "keep the batch size" loop, the NPY /
 result.json / PNG naming and contents are the reference's; additions are optional flags
 (--arch, --dtype, --drn_weights, --pool_mode, --mean_sampling, --no_figure, --balanced, --io_threads, --decode_procs:
-ProcessDecoder below, on the slabs and workers of slabs.py; the label-free driver's --png_encoder: png.py).
+ProcessDecoder below, on the slabs and workers of slabs.py; the label-free driver's --png_encoder: png.py; the labelled
+driver's --figure_renderer: figure.py).
 Under `python -m torch.distributed.run --nproc-per-node N` the labelled driver shards the image
 range like utils/create_*_labels.sh does and rank 0 writes result.json after one all_gather.
 """
@@ -26,6 +27,7 @@ import torch  # noqa: E402
 
 from . import decode_worker
 from . import dist as spdist
+from . import figure
 from . import ops
 from . import png
 from .pipeline import LabelPipeline
@@ -77,8 +79,9 @@ def _parser(extra):
     return p
 
 
-def get_args(argv=None):
-    """batch_spalign_kmeans.py:38-108"""
+def get_args(argv=None, figure_renderer=True):
+    """batch_spalign_kmeans.py:38-108.  figure_renderer: with --figure_renderer (batch_spalign_kmeans.py itself; the two
+    baseline scripts, which share these flags, keep matplotlib)."""
     extra = [('--gpu', dict(type=int, default=0)),
              ('--out_dir', dict(type=str, default='data/test_images')),
              ('--img_file_list', dict(type=str, default=None)),
@@ -89,7 +92,17 @@ def get_args(argv=None):
              ('--cityscapes_img_zip', dict(type=str, default=None)),
              ('--cityscapes_label_zip', dict(type=str, default=None)),
              ('--camera_param_dir', dict(type=str, default='data/camera'))]
-    args = _parser(extra).parse_args(argv)
+    if figure_renderer:
+        # matplotlib: the 2x2 figure of :361-386, <name>.png (every byte as before); device: the four panels composed
+        # and JPEG-encoded on the device (figure.py), <stem>.jpg
+        extra.append(('--figure_renderer', dict(type=str, default='matplotlib', choices=['matplotlib', 'device'])))
+    parser = _parser(extra)
+    args = parser.parse_args(argv)
+    if getattr(args, 'figure_renderer', 'matplotlib') == 'device':
+        if args.host_resize:
+            parser.error('--figure_renderer device needs the frames on the device: not with --host_resize')
+        if args.no_figure:
+            parser.error('--figure_renderer device draws figures: not with --no_figure')
     args.resize_shape = tuple(args.resize_shape)
     os.makedirs(args.out_dir, exist_ok=True)
     return args
@@ -97,7 +110,7 @@ def get_args(argv=None):
 
 def get_args_direct(argv=None):
     """direct_clustering.py:38-108 — the labelled driver's flags with --n_clusters 4."""
-    args = get_args(argv)
+    args = get_args(argv, figure_renderer=False)
     return args
 
 
@@ -112,7 +125,7 @@ def get_args_overlaps(argv=None):
     for flag, val in (('--felzenszwalb_scale', '500.0'), ('--felzenszwalb_sigma', '0.9')):
         if flag not in rest:
             defaults += [flag, val]
-    args = get_args(defaults + rest)
+    args = get_args(defaults + rest, figure_renderer=False)
     args.overlap_threshold = known.overlap_threshold
     return args
 
@@ -311,10 +324,11 @@ class ImageList(object):
         img = _decode(src)
         return np.ascontiguousarray(img if img.ndim == 2 else img[:, :, 0])
 
-    def batch_device(self, lo, hi, pool, engine, ring=None):
+    def batch_device(self, lo, hi, pool, engine, ring=None, want_u8=False):
         """dataset[lo:hi] as a (B,3,h,w) float32 CUDA tensor: decode on the worker threads, upload the
         8-bit images (3 bytes per pixel) and resize on the GPU (spa_resize_bicubic_u8: bit exact with the
-        Pillow resize of `get`).  Falls back to `batch` when the images of the batch differ in size."""
+        Pillow resize of `get`).  Falls back to `batch` when the images of the batch differ in size.
+        want_u8: -> (that batch, the uploaded full-size (B,H,W,3) uint8 batch or None after the fall-back)."""
         idx = list(range(len(self))[lo:hi])
         raw = list(pool.map(self.get_raw, idx)) if pool is not None else [self.get_raw(i) for i in idx]
         if len({r.shape for r in raw}) != 1 or raw[0].shape[2] != 3:
@@ -325,14 +339,16 @@ class ImageList(object):
                 if self._shape is not None and tuple(img.shape[1:]) != tuple(self._shape):
                     img = resize_bicubic_chw(img, self._shape)
                 return img.astype(self._dtype)
-            return np.stack(list(pool.map(host, raw)) if pool is not None else [host(r) for r in raw])
+            t = np.stack(list(pool.map(host, raw)) if pool is not None else [host(r) for r in raw])
+            return (t, None) if want_u8 else t
         if ring is None:
             if not hasattr(self, '_ring'):
                 self._ring = PinnedRing()
             ring = self._ring
         u8 = ring.upload(raw, engine.device, pool)
         shape = tuple(self._shape) if self._shape is not None else raw[0].shape[:2]
-        return engine.resize_u8(u8, shape, RESIZE_BACKEND[0])
+        t = engine.resize_u8(u8, shape, RESIZE_BACKEND[0])
+        return (t, u8) if want_u8 else t
 
     def batch(self, lo, hi, pool=None):
         """dataset[lo:hi] stacked (python slice semantics, like concat_examples(dataset[i:end_i]));
@@ -490,6 +506,8 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
     `make_model`: factory replacing create_model (tests of the host logic inject a stub)."""
     args = (get or get_args)(argv)
     RESIZE_BACKEND[0] = getattr(args, 'resize_backend', 'pil')
+    # not an entry of vars(args): the result.json lines are the same under either renderer
+    renderer = args.__dict__.pop('figure_renderer', 'matplotlib')
     rank, ws, local = spdist.init()
     if ws > 1:
         args.gpu = local
@@ -513,15 +531,19 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
     ranges = [(max(lo, 0), hi) for lo, hi in spdist.batch_ranges(start, end, args.batchsize)] if end > start else []
     path = os.path.join(args.out_dir, 'result.json')
 
-    def finish(i, rm, cl, n_sp, info, times, st_all, conf=None, gt_raw=None):
+    def finish(i, rm, cl, n_sp, info, times, st_all, conf=None, gt_raw=None, fig=None):
         """Everything the reference does per image after the masks exist (:461-483, :388-424).  conf: the
         image's {TN, FP, FN, TP} already counted on the device against its ground truth, with rm / cl already at
-        the ground truth's size (the asynchronous loop); otherwise decode, resize and count here."""
+        the ground truth's size (the asynchronous loop); otherwise decode, resize and count here.  fig: (figures, slot,
+        j) of the image's overview figure encoded on the device (--figure_renderer device): <stem>.jpg."""
         img_fn, label_fn = imgs_ds._paths[i], labels_ds._paths[i]
         if conf is not None:
             save_npy(args, img_fn, rm, cl)
             gt = None
-            if not args.no_figure:
+            if fig is not None:
+                png.write_file(os.path.join(args.out_dir, os.path.splitext(os.path.basename(img_fn))[0] + '.jpg'),
+                               fig[0].file_bytes(fig[1], fig[2]))
+            elif not args.no_figure:
                 gt = create_label_mask(gt_raw)
                 full = _decode(imgs_ds._open(img_fn) if imgs_ds._open else img_fn)   # :464 reloads the PNG
                 save_figure(args, full, rm, gt, cl, img_fn)
@@ -566,6 +588,7 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
     pending = []
     keep = []               # pinned buffers the writers of `pending` read from
     decoder = None
+    figures = {}            # --figure_renderer device: figure.DeviceFigures per ground-truth size, and their context 'eng'
     # the asynchronous loop: LabelPipeline on the GPU (the baselines and the stub-model tests keep the simple one)
     use_async = make_pipe is None and make_model is None
     try:
@@ -595,13 +618,16 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
                             t = tls.eng.resize_u8(u8, shape, RESIZE_BACKEND[0])
                             ev = torch.cuda.Event()
                             ev.record(tls.stream)
-                            return t, ev, gts, gt_dev
+                            return t, ev, gts, gt_dev, u8
             # ground truth PNGs of the batch decode alongside its images
             gt_f = [workers.submit(labels_ds.get_gray, i) for i in idx] if use_async else None
-            gts = gt_dev = ev = None
+            gts = gt_dev = ev = u8 = None
             if have_gpu and not args.host_resize:
                 with torch.cuda.stream(tls.stream):
-                    t = imgs_ds.batch_device(lo, hi, workers, tls.eng, tls.ring)
+                    # (the figures on the device want the full-size batch that the resize read)
+                    t, u8 = imgs_ds.batch_device(lo, hi, workers, tls.eng, tls.ring, want_u8=True)
+                    if renderer != 'device':
+                        u8 = None
             else:
                 t = imgs_ds.batch(lo, hi, workers)
             if gt_f is not None:
@@ -612,7 +638,7 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
             if have_gpu and (isinstance(t, torch.Tensor) or gt_dev is not None):    # else: host arrays, nothing in flight
                 ev = torch.cuda.Event()
                 ev.record(tls.stream)
-            return t, ev, gts, gt_dev
+            return t, ev, gts, gt_dev, u8
 
         def drain_all():
             drain(pending)
@@ -624,6 +650,8 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
             decoder = open_or_none(lambda: ProcessDecoder(imgs_ds, labels_ds, args.batchsize, args.decode_procs,
                                                           ops.engine().device, host_labels=not args.no_figure),
                                    '--decode_procs: %%s; decoding on the %d io threads instead' % args.io_threads, sys.stderr)
+            if decoder is not None and renderer == 'device' and decoder.ishape[:2] == decoder.gshape:
+                decoder.host_labels = False         # every batch it delivers gets its figures on the device
         depth = 2 if use_async else 1
         queue = [loader.submit(load, lo, hi) for lo, hi in ranges[:depth]]
         if use_async:
@@ -645,6 +673,32 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
                                         torch.from_numpy(nearest_index(shape[1], m.shape[2])).to(dev))
                 ys, xs = index_cache[key]
                 return m.index_select(1, ys).index_select(2, xs)
+
+            fig_luts = (figure.overlay(), figure.two_colour([7]), figure.clusters(max(args.n_clusters, 2)),
+                        figure.two_colour([0]))
+            fig_modes = (figure.BLEND, figure.TABLE, figure.TABLE, figure.TABLE)
+            told = []
+
+            def encode_figures(u8, gt_dev, road_d, cl_d):
+                """on the current stream: the batch's 2x2 figures in matplotlib's panel order (the frame under the road
+                mask, the ground truth's road, all clusters, cluster 0) -> (figures, slot), or None where the batch's
+                ground truth is not on the device or its frames have another size: matplotlib draws those"""
+                if u8 is None or gt_dev is None or tuple(u8.shape[1:3]) != tuple(gt_dev.shape[1:]):
+                    if not told:
+                        told.append(True)
+                        print('--figure_renderer device: a batch whose ground truth is not on the device at the frames\' '
+                              'size gets matplotlib figures', file=sys.stderr)
+                    return None
+                shape = tuple(gt_dev.shape[1:])
+                if shape not in figures:
+                    # a context of its own: the JPEG kernels' workspace must not grow in the pipeline's context, where it
+                    # would make the captured DRN graph stale (drn.py, _graph_forward) and have it captured once more
+                    if 'eng' not in figures:
+                        figures['eng'] = Engine(dev.index)
+                    figures[shape] = figure.DeviceFigures(figures['eng'], shape, args.batchsize, (2, 2))
+                u8.record_stream(torch.cuda.current_stream(dev))
+                road_c, cl_c = road_d.contiguous(), cl_d.contiguous()
+                return figures[shape], figures[shape].encode(u8, [road_c, gt_dev, cl_c, cl_c], fig_luts, fig_modes)
 
             def finalize(st):
                 res = st['res']
@@ -680,24 +734,28 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
                 # the previous batch's writers finish before this batch's are queued
                 drain_all()
                 keep.append(st)
+                fig = st['fig']
+                if fig is not None:
+                    fig[0].fetch(fig[1])            # the used bytes of the batch's JPEG scans; the writers wait for them
                 for j, i in enumerate(st['idx']):
                     pending.append(workers.submit(finish, i, st['road_h'][j].numpy(), st['cl_h'][j].numpy(), int(n_sp[j]),
                                                   info, times, st['st_all'],
                                                   None if conf is None else conf[j],
-                                                  None if st['gts'] is None else st['gts'][j]))
+                                                  None if st['gts'] is None else st['gts'][j],
+                                                  None if fig is None else fig + (j,)))
 
             prev = None
             trace = os.environ.get('SPA_DRIVER_TRACE') == '1'      # host-side timeline of the loop, one line per batch
             for bi, (lo, hi) in enumerate(ranges):
                 st_all = time.time()
-                imgs, ready, gts, gt_dev = queue.pop(0).result()
+                imgs, ready, gts, gt_dev, u8 = queue.pop(0).result()
                 if bi + depth < len(ranges):
                     queue.append(loader.submit(load, ranges[bi + depth][0], ranges[bi + depth][1]))
                 t_loaded = time.time()
                 main = torch.cuda.current_stream()
                 if ready is not None:
                     main.wait_event(ready)
-                    for t in (imgs, gt_dev):
+                    for t in (imgs, gt_dev, u8):
                         if isinstance(t, torch.Tensor):
                             t.record_stream(main)
                 # join=False: the batch's tail (pooling, k-means, paint) runs on the pipeline's second stream and this stream goes
@@ -711,6 +769,7 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
                         road_d, cl_d = to_gt_size(res.road, gt_dev.shape[1:]), to_gt_size(res.cluster, gt_dev.shape[1:])
                         gtm = torch.where(gt_dev <= 6, -1, torch.where(gt_dev == 7, 1, 0)).to(torch.int32)   # :279-296
                         conf_d = eng.confusion(road_d.contiguous(), gtm)
+                    fig = encode_figures(u8, gt_dev, road_d, cl_d) if renderer == 'device' else None
                     status_h = eng.status_take_async()          # the bits raised so far (one atomic exchange, in stream order)
                     computed = torch.cuda.Event(enable_timing=True)
                     computed.record(res.stream)
@@ -718,7 +777,7 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
                 # not): a copy queue whose head is a barrier waiting a batch's time for the compute stream slows every dispatch of
                 # that batch (measured: 82 -> 77.6 ms per batch of 30 in pipeline.HostStream, tools/h2h_probe2.py)
                 st = dict(idx=list(range(len(imgs_ds)))[lo:hi], res=res, events=events, gts=gts, st_all=st_all,
-                          status_h=status_h, computed=computed, dev=(road_d, cl_d, conf_d))
+                          status_h=status_h, computed=computed, dev=(road_d, cl_d, conf_d), fig=fig)
                 t_enq = time.time()
                 if prev is not None:
                     finalize(prev)
@@ -734,7 +793,7 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
         else:
             for bi, (lo, hi) in enumerate(ranges):
                 st_all = time.time()
-                imgs, ready, _gts, _gt_dev = queue.pop(0).result()
+                imgs, ready, _gts, _gt_dev, _u8 = queue.pop(0).result()
                 if ready is not None:
                     torch.cuda.current_stream().wait_event(ready)
                     if isinstance(imgs, torch.Tensor):
@@ -762,6 +821,12 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
         loader.shutdown()
         if decoder is not None:
             decoder.close()
+        # the figures' context goes now, not whenever a collection finds it (drn.py, _graph_capture: a context freed while
+        # a later call of this function captures its graph invalidates the capture)
+        fig_eng = figures.pop('eng', None)
+        figures.clear()
+        if fig_eng is not None:
+            fig_eng.close()
     if bad:
         raise bad[0].exception()
     if ws > 1:

@@ -1371,6 +1371,55 @@ class Engine(object):
                                              self._s()))
         return out, nbytes
 
+    # ---- overview figures (figure.py)
+    def figure_compose(self, frames, planes, luts, modes, layout, decimate=4, gap=16, out=None):
+        """The overview figures of a batch (spa_figure_compose_u8) -> the canvas (B,Hc,Wc,3) uint8 on the device.
+        frames (B,H,W,3) uint8 or None; planes: 1..4 index planes (B,H,W) uint8 (they may be one tensor several times);
+        luts: per panel a (256,3) uint8 colour table on the device; modes: per panel 0 (the table's colour) or 1 (that
+        colour at 0.4 over frames); layout (rows, columns).  figure.compose_host restates the bytes and
+        figure.canvas_shape the canvas.  out: the caller's canvas; without it the engine's own, which the next call
+        without it overwrites."""
+        planes, luts, modes = list(planes), list(luts), [int(m) for m in modes]
+        P = len(planes)
+        if not (1 <= P <= 4 and len(luts) == P and len(modes) == P):
+            raise SpalignError('figure_compose: 1..4 panels, each a plane, a table and a mode (got %d, %d, %d)'
+                               % (P, len(luts), len(modes)))
+        shape = tuple(_req(planes[0], torch.uint8, 'planes[0]').shape)
+        if len(shape) != 3 or min(shape) <= 0:
+            raise SpalignError('figure_compose: a plane must be (B,H,W) uint8, got %s' % (shape,))
+        for p in range(P):
+            if tuple(_req(planes[p], torch.uint8, 'planes[%d]' % p).shape) != shape:
+                raise SpalignError('figure_compose: planes[%d] is %s, planes[0] %s' % (p, tuple(planes[p].shape), shape))
+            if tuple(_req(luts[p], torch.uint8, 'luts[%d]' % p).shape) != (256, 3):
+                raise SpalignError('figure_compose: luts[%d] must be (256,3) uint8' % p)
+            if modes[p] not in (0, 1):
+                raise SpalignError('figure_compose: modes[%d] must be 0 or 1, got %d' % (p, modes[p]))
+        B, H, W = shape
+        if frames is not None and tuple(_req(frames, torch.uint8, 'frames').shape) != (B, H, W, 3):
+            raise SpalignError('figure_compose: frames must be %s uint8, got %s' % ((B, H, W, 3), tuple(frames.shape)))
+        if frames is None and any(modes):
+            raise SpalignError('figure_compose: a blended panel needs frames')
+        R, C = (int(v) for v in layout)
+        d, g = int(decimate), int(gap)
+        hc, wc = ctypes.c_int32(0), ctypes.c_int32(0)
+        if R < 1 or C < 1 or R * C < P or self._lib.spa_figure_canvas_shape(H, W, R, C, d, g, ctypes.byref(hc),
+                                                                            ctypes.byref(wc)) != _lib.SPA_OK:
+            raise SpalignError('figure_compose: %d panels in a %d x %d layout, decimation %d (1..16), gap %d (0..64)'
+                               % (P, R, C, d, g))
+        Hc, Wc = hc.value, wc.value
+        if out is None:
+            own = getattr(self, '_figure_out', None)
+            if own is None or own.numel() < B * Hc * Wc * 3:
+                own = self._figure_out = torch.empty((B * Hc * Wc * 3,), dtype=torch.uint8, device=self.device)
+            out = own[:B * Hc * Wc * 3].view(B, Hc, Wc, 3)
+        if tuple(_req(out, torch.uint8, 'out').shape) != (B, Hc, Wc, 3):
+            raise SpalignError('figure_compose: out must be %s uint8, got %s' % ((B, Hc, Wc, 3), tuple(out.shape)))
+        check(self._lib.spa_figure_compose_u8(self._ctx, _ptr(frames), B, H, W, P,
+                                              (ctypes.c_void_p * P)(*[t.data_ptr() for t in planes]),
+                                              (ctypes.c_void_p * P)(*[t.data_ptr() for t in luts]),
+                                              (ctypes.c_int32 * P)(*modes), R, C, d, g, _ptr(out), Hc, Wc, self._s()))
+        return out
+
 
 _DEFAULT = None
 

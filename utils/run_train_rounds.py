@@ -39,7 +39,8 @@ train_segnet.py --loader_procs: decode workers per rank and the input stage on t
 job needs n_gpus x loader_procs CPUs for them; they also feed those rounds' validation), --label_loader_procs (the
 labelling passes' labels_from_segnet.py --loader_procs: decode workers per labelling process, independent of
 --loader_procs; the job needs n_gpus x label_loader_procs CPUs for them), --n_labels (overrides the
-split's constant), --no_figure (the labellers' 3-panel figures), --child_timeout.
+split's constant), --no_figure (the labellers' 3-panel figures), --figure_renderer (labels_from_segnet.py's: matplotlib,
+the default, or device: the labelling processes compose and JPEG-encode the figures on the GPU), --child_timeout.
 plan() computes the rounds, their commands, resume paths, result-directory prefixes and zip names without launching
 anything.
 """
@@ -112,6 +113,8 @@ def get_parser():
                              "0: none")
     parser.add_argument('--n_labels', type=int, default=None, help='images to relabel (default: the split size)')
     parser.add_argument('--no_figure', action='store_true', default=False)
+    parser.add_argument('--figure_renderer', type=str, default='matplotlib', choices=['matplotlib', 'device'],
+                        help="the labelling processes' save_labels(figure_renderer=...)")
     parser.add_argument('--child_timeout', type=float, default=0,
                         help='seconds one child (a training round or a labelling pass) may take; 0: no limit')
     return parser
@@ -343,7 +346,8 @@ def label_worker(spec):
                     spec['save_each'], figure=spec['figure'], result_fn=os.path.join(spool, 'result.json'),
                     on_labels=None if spec['save_each'] else spool_one,
                     split_planes=spec.get('split_planes', False), dtype=spec['dtype'],
-                    loader_procs=spec.get('loader_procs', 0))
+                    loader_procs=spec.get('loader_procs', 0),
+                    figure_renderer=spec.get('figure_renderer', 'matplotlib'))
 
 
 def _child_main(target, arg, parent_pid):
@@ -422,7 +426,7 @@ def label_specs(args, param_dir, iteration, out_dir):
                       'start': start, 'end': end, 'soft_label': soft_label, 'eval_shape': list(args.eval_shape),
                       'save_each': args.save_each, 'figure': not args.no_figure, 'dtype': args.label_dtype,
                       'split_planes': args.label_split_planes, 'loader_procs': args.label_loader_procs,
-                      'spool': os.path.join(spool_root, 'w%d' % i)})
+                      'figure_renderer': getattr(args, 'figure_renderer', 'matplotlib'), 'spool': os.path.join(spool_root, 'w%d' % i)})
     return specs
 
 
