@@ -58,6 +58,7 @@ class Engine(object):
         check(self._lib.spa_ctx_create(self.device.index, ctypes.byref(h)))
         self._ctx = h
         self._in_tables = {}           # segnet_train_input / _label: device tables per (kind, n_in, n_out, backend)
+        self._stream_own = {}          # png_deflate / jpeg_encode: the engine's own out and meta (_stream_out)
 
     def _s(self):
         """The launch stream: torch's current stream of THIS engine's device (a spa_ctx is bound to one
@@ -1298,30 +1299,37 @@ class Engine(object):
                 self._in_tables[key] = tuple(torch.from_numpy(t.astype(np.int32)).to(self.device)
                                              for t in png.nearest_tables((Hs, Ws), (Ho, Wo)))
             rows, cols = self._in_tables[key]
-        if out is None:
-            stride = (int(self._lib.spa_png_deflate_bound(Ho, Wo)) + 15) // 16 * 16
-            own = getattr(self, '_png_out', None)
-            if own is None or own.shape[0] < B or own.shape[1] < stride:
-                own = self._png_out = torch.empty((B, max(stride, 16)), dtype=torch.uint8, device=self.device)
-            out = own[:B]
-        if nbytes is None or adler is None:
-            own = getattr(self, '_png_meta', None)
-            if own is None or own.shape[1] < B:
-                own = self._png_meta = torch.empty((2, B), dtype=torch.int32, device=self.device)
-            nbytes = own[0, :B] if nbytes is None else nbytes
-            adler = own[1, :B] if adler is None else adler
-        if not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1):
-            raise SpalignError('png_deflate: out must be a (B,stride) uint8 CUDA tensor with contiguous rows')
-        if out.shape[1] < int(self._lib.spa_png_deflate_bound(Ho, Wo)):
-            raise SpalignError('png_deflate: a row of out holds %d bytes, spa_png_deflate_bound(%d, %d) is %d'
-                               % (out.shape[1], Ho, Wo, int(self._lib.spa_png_deflate_bound(Ho, Wo))))
-        for t, what in ((nbytes, 'nbytes'), (adler, 'adler')):
-            if tuple(_req(t, torch.int32, what).shape) != (B,):
-                raise SpalignError('png_deflate: %s must be (%d,) int32' % (what, B))
+        out, (nbytes, adler), stride = self._stream_out(
+            'png_deflate', B, int(self._lib.spa_png_deflate_bound(Ho, Wo)), 'spa_png_deflate_bound(%d, %d)' % (Ho, Wo),
+            out, (('nbytes', nbytes), ('adler', adler)))
         check(self._lib.spa_png_deflate_u8(self._ctx, _ptr(src), B, Hs, Ws, _ptr(rows), _ptr(cols), Ho, Wo, _ptr(out),
-                                           int(out.stride(0)) if B > 1 else int(out.shape[1]), _ptr(nbytes),
-                                           _ptr(adler), self._s()))
+                                           stride, _ptr(nbytes), _ptr(adler), self._s()))
         return out, nbytes, adler
+
+    def _stream_out(self, name, B, bound, bound_name, out, meta):
+        """What png_deflate and jpeg_encode share: the caller's out (B,stride) uint8 and int32 meta vectors (B), checked,
+        or, where one is None, the engine's own for `name`: allocated once, overwritten by the next call without.
+        bound: the bytes a row must hold; meta: ((what, tensor or None), ...) -> (out, the meta vectors, the row stride
+        to pass down)."""
+        own = self._stream_own.setdefault(name, {})
+        if out is None:
+            stride = max((bound + 15) // 16 * 16, 16)
+            if 'out' not in own or own['out'].shape[0] < B or own['out'].shape[1] < stride:
+                own['out'] = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
+            out = own['out'][:B]
+        if any(t is None for _, t in meta):
+            if 'meta' not in own or own['meta'].shape[1] < B:
+                own['meta'] = torch.empty((len(meta), B), dtype=torch.int32, device=self.device)
+            meta = [(what, own['meta'][i, :B] if t is None else t) for i, (what, t) in enumerate(meta)]
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1):
+            raise SpalignError('%s: out must be a (B,stride) uint8 CUDA tensor with contiguous rows' % name)
+        if out.shape[1] < bound:
+            raise SpalignError('%s: a row of out holds %d bytes, %s is %d' % (name, out.shape[1], bound_name, bound))
+        for what, t in meta:
+            if tuple(_req(t, torch.int32, what).shape) != (B,):
+                raise SpalignError('%s: %s must be (%d,) int32' % (name, what, B))
+        # (a one-row tensor's stride(0) need not be its row length, and nothing steps over it)
+        return out, [t for _, t in meta], int(out.stride(0)) if B > 1 else int(out.shape[1])
 
     # ---- JPEG frames (jpeg.py)
     def jpeg_encode(self, rgb, Ri=None, out=None, nbytes=None, coef=None):
@@ -1340,35 +1348,18 @@ class Engine(object):
         if B <= 0 or bound <= 0:
             raise SpalignError('jpeg_encode: %d frames of %d x %d (multiples of 16) with a restart interval of %d MCUs'
                                % (B, H, W, Ri))
-        if out is None:
-            stride = (bound + 15) // 16 * 16
-            own = getattr(self, '_jpeg_out', None)
-            if own is None or own.shape[0] < B or own.shape[1] < stride:
-                own = self._jpeg_out = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
-            out = own[:B]
-        if nbytes is None:
-            own = getattr(self, '_jpeg_meta', None)
-            if own is None or own.shape[0] < B:
-                own = self._jpeg_meta = torch.empty((B,), dtype=torch.int32, device=self.device)
-            nbytes = own[:B]
+        out, (nbytes,), stride = self._stream_out('jpeg_encode', B, bound, 'spa_jpeg_scan_bound(%d, %d, %d)' % (H, W, Ri),
+                                                  out, (('nbytes', nbytes),))
         n_coef = B * H * W * 3 // 2
         if coef is None:
             own = getattr(self, '_jpeg_coef', None)
             if own is None or own.numel() < n_coef:
                 own = self._jpeg_coef = torch.empty((n_coef,), dtype=torch.int16, device=self.device)
             coef = own
-        if not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1):
-            raise SpalignError('jpeg_encode: out must be a (B,stride) uint8 CUDA tensor with contiguous rows')
-        if out.shape[1] < bound:
-            raise SpalignError('jpeg_encode: a row of out holds %d bytes, spa_jpeg_scan_bound(%d, %d, %d) is %d'
-                               % (out.shape[1], H, W, Ri, bound))
-        if tuple(_req(nbytes, torch.int32, 'nbytes').shape) != (B,):
-            raise SpalignError('jpeg_encode: nbytes must be (%d,) int32' % B)
         if _req(coef, torch.int16, 'coef').numel() < n_coef:
             raise SpalignError('jpeg_encode: coef must hold %d int16' % n_coef)
-        check(self._lib.spa_jpeg_encode_rgb8(self._ctx, _ptr(rgb), B, H, W, Ri, _ptr(coef), _ptr(out),
-                                             int(out.stride(0)) if B > 1 else int(out.shape[1]), _ptr(nbytes),
-                                             self._s()))
+        check(self._lib.spa_jpeg_encode_rgb8(self._ctx, _ptr(rgb), B, H, W, Ri, _ptr(coef), _ptr(out), stride,
+                                             _ptr(nbytes), self._s()))
         return out, nbytes
 
     # ---- overview figures (figure.py)

@@ -4,7 +4,8 @@ Engine.figure_compose (spa_figure_compose_u8, csrc/spa_figure.hip) lays up to fo
 each panel is a decimated view of an index plane coloured through a 256-entry table, alone or blended at 0.4 over the
 frame; Engine.jpeg_encode turns the canvas into a JPEG scan and jpeg.assemble into a file.  The bytes are this
 project's, not matplotlib's (no titles, no Agg resampling, no per-image colour normalisation); they are fixed in
-include/spalign.h so that the device and `compose_host` can be compared byte for byte.
+include/spalign.h so that the device and `compose_host` can be compared byte for byte.  DeviceFigures is what the batch
+loops use: jpeg.DeviceEncoder with a canvas in each set of its buffer ring (devenc.Ring).
 
 compose_host is the numpy restatement of that format, written for the tests; it is never on a product path.  The
 colour tables below are data: matplotlib's viridis as 8-bit colours (cm.viridis(np.arange(256), bytes=True)) and the
@@ -137,10 +138,10 @@ def overlay():
 
 
 # ------------------------------------------------------------------------------- the batch loops' helper
-class DeviceFigures(object):
+class DeviceFigures(jpeg.DeviceEncoder):
     """What a batch loop needs to store overview figures as JPEG files: jpeg.DeviceEncoder for the canvas of (H, W)
-    sources in `layout`, and two canvases, allocated once for batches of at most `batch` images.  Per batch, as with
-    jpeg.DeviceEncoder:
+    sources in `layout`, each of its sets (devenc.Ring) with a canvas of its own, allocated once for batches of at most
+    `batch` images.  Per batch, as with jpeg.DeviceEncoder:
 
       slot = encode(frames, planes, luts, modes)   on the current stream: compose, then the scans and their lengths.
                                                    luts: numpy tables (uploaded once each) or device tensors.
@@ -150,12 +151,10 @@ class DeviceFigures(object):
 
     def __init__(self, engine, shape, batch, layout, decimate=DEFAULT_DECIMATE, gap=DEFAULT_GAP, Ri=jpeg.DEFAULT_RI):
         import torch
-        self.eng, self.layout, self.decimate, self.gap = engine, tuple(int(v) for v in layout), int(decimate), int(gap)
-        self.shape = (int(shape[0]), int(shape[1]))
-        self.canvas = canvas_shape(self.shape[0], self.shape[1], self.layout, self.decimate, self.gap)
-        B = max(int(batch), 1)
-        self.enc = jpeg.DeviceEncoder(engine, self.canvas, B, Ri)
-        self.canvases = [torch.empty((B,) + self.canvas + (3,), dtype=torch.uint8, device=engine.device) for _ in range(2)]
+        self.layout, self.decimate, self.gap = tuple(int(v) for v in layout), int(decimate), int(gap)
+        canvas = canvas_shape(int(shape[0]), int(shape[1]), self.layout, self.decimate, self.gap)
+        jpeg.DeviceEncoder.__init__(self, engine, canvas, batch, Ri)         # self.shape: the canvas'
+        self.declare('canvas', (self.batch,) + canvas + (3,), torch.uint8)
         self._luts = {}
 
     def lut(self, table):
@@ -169,17 +168,7 @@ class DeviceFigures(object):
 
     def encode(self, frames, planes, luts, modes):
         n = int(planes[0].shape[0])
-        canvas = self.canvases[self.enc.count % 2][:n]
+        canvas = self.next_slot()['canvas'][:n]
         self.eng.figure_compose(frames, planes, [self.lut(t) for t in luts], modes, self.layout, self.decimate, self.gap,
                                 out=canvas)
-        return self.enc.encode(canvas)
-
-    def fetch(self, slot):
-        self.enc.fetch(slot)
-
-    def file_bytes(self, slot, j):
-        return self.enc.file_bytes(slot, j)
-
-    @property
-    def downloaded(self):
-        return self.enc.downloaded
+        return jpeg.DeviceEncoder.encode(self, canvas)

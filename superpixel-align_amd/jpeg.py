@@ -8,11 +8,14 @@ markers); they are fixed in include/spalign.h so that the device and `encode_hos
 
 encode_host is the plain numpy / Python restatement of that format, written for the tests; it is never on a product
 path.  The tables below are data: the quality-75 quantisation tables and the standard Huffman tables as Pillow writes
-them (tests/test_jpeg_device_cpu.py reads them back out of a file Pillow writes).
+them (tests/test_jpeg_device_cpu.py reads them back out of a file Pillow writes).  DeviceEncoder is what the batch
+loops use: devenc.Ring, the buffer ring of every device encoder, with this module's bound, engine call and framing.
 """
 import struct
 
 import numpy as np
+
+from . import devenc
 
 MCU = 16                                                 # pixels per side of a 4:2:0 minimum coded unit
 DEFAULT_RI = 4                                           # restart interval in MCUs (README "JPEG frames on the device": why 4)
@@ -256,69 +259,28 @@ def assemble(scan_bytes, H, W, Ri):
     return header(H, W, Ri) + bytes(scan_bytes) + b'\xff\xd9'
 
 
-class DeviceEncoder(object):
-    """What a batch loop needs to store JPEG frames from device images: two buffer sets, each the device scan buffer,
-    the coefficient workspace and the lengths, and their pinned copies, allocated once for batches of at most `batch`
-    frames of `shape`.  Per batch, in this order (png.DeviceEncoder's):
+class DeviceEncoder(devenc.Ring):
+    """devenc.Ring for JPEG frames from device images: encode(frames) leaves the scans of frames (n,H,W,3) uint8 with
+    their lengths (each set has its own coefficient workspace), file_bytes(slot, j) is frame j's JPEG file.
+    pinned_bytes: the ring's first pinned buffer; by default a byte per pixel, far above what quality 75 takes."""
 
-      slot = encode(frames)   on the current stream: the scans of frames (n,H,W,3) uint8, then the lengths into pinned
-                              memory.  Nothing waits.
-      fetch(slot)             once the host knows that stream got past encode(): the download of the USED bytes only,
-                              on the encoder's own stream.
-      file_bytes(slot, j)     any thread: waits for that download, -> the bytes of frame j's JPEG file.
-
-    A set is reused by the batch after next: encode() makes the device wait for the set's last download, and the
-    caller must be through with file_bytes() of a set before it calls fetch() on it again.  The pinned scan buffer
-    holds the batch's scans one after the other; it starts at a byte per pixel, far above what quality 75 takes, and
-    fetch() replaces it by a larger one if a batch ever needs that."""
-
-    def __init__(self, engine, shape, batch, Ri=DEFAULT_RI):
+    def __init__(self, engine, shape, batch, Ri=DEFAULT_RI, pinned_bytes=None):
         import torch
         H, W, self.Ri = check_shape(shape[0], shape[1], Ri)
-        self.eng, self.shape = engine, (H, W)
+        self.shape = (H, W)
         bound = scan_bound(H, W, self.Ri)
         if bound > (1 << 31) - 1:
             raise ValueError('jpeg.DeviceEncoder: the scan of a %d x %d frame may not fit 2^31 - 1 bytes' % self.shape)
-        B, stride = max(int(batch), 1), (bound + 15) // 16 * 16
-        n_coef = B * (H // MCU) * (W // MCU) * 384
-        self.slots = [dict(out=torch.empty((B, stride), dtype=torch.uint8, device=engine.device),
-                           coef=torch.empty((n_coef,), dtype=torch.int16, device=engine.device),
-                           meta=torch.empty((B,), dtype=torch.int32, device=engine.device),
-                           out_h=torch.empty((min(B * H * W, B * stride),), dtype=torch.uint8).pin_memory(),
-                           meta_h=torch.empty((B,), dtype=torch.int32).pin_memory(), copied=None, n=0)
-                      for _ in range(2)]
-        self.stream = torch.cuda.Stream(device=engine.device)
-        self.count = 0
-        self.downloaded = 0                 # scan bytes fetched so far
+        B = max(int(batch), 1)
+        if pinned_bytes is None:
+            pinned_bytes = min(B * H * W, B * ((bound + 15) // 16 * 16))
+        devenc.Ring.__init__(self, engine, B, bound, 1, pinned_bytes)
+        self.declare('coef', (B * (H // MCU) * (W // MCU) * 384,), torch.int16)
 
-    def encode(self, frames):
-        import torch
-        slot = self.slots[self.count % 2]
-        self.count += 1
-        n = slot['n'] = int(frames.shape[0])
-        if slot['copied'] is not None:
-            torch.cuda.current_stream(self.eng.device).wait_event(slot['copied'])
-        self.eng.jpeg_encode(frames, self.Ri, out=slot['out'][:n], nbytes=slot['meta'][:n], coef=slot['coef'])
-        slot['meta_h'].copy_(slot['meta'], non_blocking=True)
-        return slot
+    def launch(self, slot, frames, n):
+        self.eng.jpeg_encode(frames, self.Ri, out=slot['out'][:n], nbytes=slot['meta'][0, :n], coef=slot['coef'])
 
-    def fetch(self, slot):
-        import torch
-        lengths = slot['lengths'] = [int(v) for v in slot['meta_h'].numpy()[:slot['n']]]
-        starts = slot['starts'] = [0]
-        for nb in lengths:
-            starts.append(starts[-1] + (nb + 15) // 16 * 16)
-        if starts[-1] > slot['out_h'].numel():
-            slot['out_h'] = torch.empty((starts[-1],), dtype=torch.uint8).pin_memory()
-        with torch.cuda.stream(self.stream):
-            for j, nb in enumerate(lengths):
-                slot['out_h'][starts[j]:starts[j] + nb].copy_(slot['out'][j, :nb], non_blocking=True)
-                self.downloaded += nb
-            slot['copied'] = torch.cuda.Event()
-            slot['copied'].record(self.stream)
+    def frame(self, slot, j, payload):
+        return assemble(payload, self.shape[0], self.shape[1], self.Ri)
 
-    def file_bytes(self, slot, j):
-        slot['copied'].synchronize()
-        lo = slot['starts'][j]
-        return assemble(slot['out_h'][lo:lo + slot['lengths'][j]].numpy().tobytes(), self.shape[0], self.shape[1],
-                        self.Ri)
+

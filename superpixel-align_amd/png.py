@@ -8,12 +8,15 @@ bytes; the bytes of Pillow's (or OpenCV's) files are not: another encoder, anoth
 
 deflate_rle_host is the plain numpy / Python restatement of the format fixed in include/spalign.h, written for the
 tests; it is never on a product path.  nearest_tables is cv.INTER_NEAREST's index arithmetic (cli.resize_nearest),
-held here once for the host resize and for the tables the encoder gathers through.
+held here once for the host resize and for the tables the encoder gathers through.  DeviceEncoder is what the batch
+loops use: devenc.Ring, the buffer ring of every device encoder, with this module's bound, engine call and framing.
 """
 import struct
 import zlib
 
 import numpy as np
+
+from . import devenc
 
 SIGNATURE = b'\x89PNG\r\n\x1a\n'
 FRAMING_BYTES = 8 + (12 + 13) + 12 + 12                  # signature, IHDR, IDAT's length / tag / CRC, IEND = 57
@@ -146,65 +149,26 @@ def deflate_rle_host(img, row_idx=None, col_idx=None):
     return bits.finish(), zlib.adler32(rows.tobytes()) & 0xffffffff
 
 
-class DeviceEncoder(object):
-    """What a batch loop needs to write label PNGs from device masks: two buffer sets, each the device stream buffer,
-    its lengths and Adler sums, and their pinned copies, allocated once for batches of at most `batch` images of
-    `shape`.  Per batch, in this order:
+class DeviceEncoder(devenc.Ring):
+    """devenc.Ring for label PNGs from device masks: encode(masks) leaves the streams of masks (n,Hs,Ws) uint8 at
+    `shape` (nearest resize inside the encoder) with their lengths and Adler sums, file_bytes(slot, j) is image j's
+    PNG file.  pinned_bytes: the ring's first pinned buffer; by default every row's bound, so that none follows."""
 
-      slot = encode(masks)    on the current stream: the streams of masks (n,Hs,Ws) uint8 at `shape` (nearest resize
-                              inside the encoder), then the lengths and sums into pinned memory.  Nothing waits.
-      fetch(slot)             once the host knows that stream got past encode(): the download of the USED bytes only,
-                              on the encoder's own stream (it does not queue behind the caller's next batch).
-      file_bytes(slot, j)     any thread: waits for that download, -> the bytes of image j's PNG file.
-
-    A set is reused by the batch after next: encode() makes the device wait for the set's last download, and the
-    caller must be through with file_bytes() of a set before it calls fetch() on it again."""
-
-    def __init__(self, engine, shape, batch):
-        import torch
-        self.eng, self.shape = engine, (int(shape[0]), int(shape[1]))
+    def __init__(self, engine, shape, batch, pinned_bytes=None):
+        self.shape = (int(shape[0]), int(shape[1]))
         bound = deflate_bound(*self.shape)
         if bound + ZLIB_BYTES > IDAT_MAX:
             raise ValueError('png.DeviceEncoder: the payload of a %d x %d image may not fit one IDAT chunk' % self.shape)
-        B, stride = max(int(batch), 1), (bound + 15) // 16 * 16
-        self.slots = [dict(out=torch.empty((B, stride), dtype=torch.uint8, device=engine.device),
-                           meta=torch.empty((2, B), dtype=torch.int32, device=engine.device),
-                           out_h=torch.empty((B, stride), dtype=torch.uint8).pin_memory(),
-                           meta_h=torch.empty((2, B), dtype=torch.int32).pin_memory(), copied=None, n=0)
-                      for _ in range(2)]
-        self.stream = torch.cuda.Stream(device=engine.device)
-        self.count = 0
-        self.downloaded = 0                 # payload bytes fetched so far
+        if pinned_bytes is None:
+            pinned_bytes = max(int(batch), 1) * ((bound + 15) // 16 * 16)
+        devenc.Ring.__init__(self, engine, batch, bound, 2, pinned_bytes)
 
-    def encode(self, masks):
-        import torch
-        slot = self.slots[self.count % 2]
-        self.count += 1
-        n = slot['n'] = int(masks.shape[0])
-        if slot['copied'] is not None:
-            torch.cuda.current_stream(self.eng.device).wait_event(slot['copied'])
+    def launch(self, slot, masks, n):
         self.eng.png_deflate(masks, self.shape, out=slot['out'][:n], nbytes=slot['meta'][0, :n],
                              adler=slot['meta'][1, :n])
-        slot['meta_h'].copy_(slot['meta'], non_blocking=True)
-        return slot
 
-    def fetch(self, slot):
-        import torch
-        # host copies: the set's next encode() overwrites meta_h while file_bytes() of this batch may still run
-        lengths, adler = ([int(v) for v in row[:slot['n']]] for row in slot['meta_h'].numpy())
-        slot['lengths'], slot['adler'] = lengths, [v & 0xffffffff for v in adler]
-        with torch.cuda.stream(self.stream):
-            for j in range(slot['n']):
-                nb = lengths[j]
-                slot['out_h'][j, :nb].copy_(slot['out'][j, :nb], non_blocking=True)
-                self.downloaded += nb
-            slot['copied'] = torch.cuda.Event()
-            slot['copied'].record(self.stream)
-
-    def file_bytes(self, slot, j):
-        slot['copied'].synchronize()
-        nb = slot['lengths'][j]
-        return assemble(slot['out_h'][j, :nb].numpy().tobytes(), slot['adler'][j], self.shape[0], self.shape[1])
+    def frame(self, slot, j, payload):
+        return assemble(payload, slot['rows'][1][j] & 0xffffffff, self.shape[0], self.shape[1])
 
 
 def write_file(fn, data):
