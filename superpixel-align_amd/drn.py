@@ -32,9 +32,11 @@ Module names follow the upstream checkpoint (conv1/bn1/layerN.M.convK/downsample
 `drn_c_26-ddedf421.pth` / `drn_d_22-4bd2f8ea.pth` load with load_state_dict, and
 `models/drn_c_26.npz` (Chainer) loads through `load_chainer_npz`.
 """
+import collections
 import gc
 import math
 import os
+from functools import partial
 
 import numpy as np
 import torch
@@ -131,148 +133,255 @@ def _graph_wanted(x):
     return x.shape[0] * x.shape[2] * x.shape[3] <= int(os.environ.get('SPA_DRN_GRAPH_PIXELS', str(4 << 20)))
 
 
-def conv_bias_act(conv, bn, x, residual=None, relu=True):
-    """relu?(bn(conv(x)) [+ residual]).  With BatchNorm folded (bn is Identity, conv carries the
-    bias) and the tensors on the GPU in channels-last storage, the bias add, the residual add and
-    the ReLU run as ONE in-place pass of libspalign (spa_bias_act) behind the MIOpen convolution
-    instead of two or three separate elementwise kernels."""
-    eng = _EPILOGUE['engine']
-    if (eng is not None and x.is_cuda and isinstance(bn, nn.Identity) and conv.bias is not None
-            and x.dtype in (torch.float32, torch.bfloat16)):
-        packed = getattr(conv, '_spa_packed', None)
-        if (packed is not None and x.dtype == torch.bfloat16 and _EPILOGUE['own_conv']
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and (residual is None or residual.is_contiguous(memory_format=torch.channels_last))):
-            # the heavy 3x3 (dilated) layers: libspalign's bf16 implicit GEMM with bias / residual / ReLU
-            # in its epilogue (no separate elementwise pass, one rounding to bf16)
-            _EPILOGUE['conv_flops'] += 2.0 * x.shape[0] * x.shape[2] * x.shape[3] * conv.out_channels * 9 * conv.in_channels
-            return eng.conv3x3_bf16(x, packed[0], packed[1], residual, relu, conv.dilation[0])
-        light = getattr(conv, '_spa_light', None)
-        if (light is not None and x.dtype == torch.bfloat16 and _EPILOGUE['own_conv'] and os.environ.get('SPA_BF16_LIGHT', '1') != '0'
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and (residual is None or residual.is_contiguous(memory_format=torch.channels_last))):
-            # the light layers of the bf16 network (stride 2, 16 / 32 channels, 1x1 projections): libspalign's plain bf16 kernel
-            opx = x.shape[0] * -(-x.shape[2] // conv.stride[0]) * -(-x.shape[3] // conv.stride[1])
-            _EPILOGUE['light_flops'] += 2.0 * opx * conv.out_channels * light[0].shape[1] * conv.in_channels
-            _EPILOGUE['light_bytes'] += 2.0 * (x.shape[0] * x.shape[2] * x.shape[3] * conv.in_channels
-                                               + opx * conv.out_channels * (2 if residual is not None else 1))
-            _EPILOGUE['light_launches'] += 1
-            return eng.conv_bf16_light(x, light[0], light[1], residual, relu, conv.stride[0], conv.dilation[0])
-        tile = _EPILOGUE['winograd']                   # 4 (default), 2 or 0/False
-        wino = getattr(conv, '_spa_wino', {}).get(4 if tile == 4 else 2) if tile else None
-        # with the split-plane kernels the direct form wins below 256 input channels (30 x 128 x 256 pixels, ms Winograd /
-        # direct: 128 -> 128 1.10 / 0.99, 128 -> 256 1.85 / 1.61, 256 -> 256 2.65 / 3.09, 256 -> 512 4.28 / 5.35)
-        if (wino is not None and _EPILOGUE['split_gemm'] and conv.in_channels < int(os.environ.get('SPA_WINO_MIN_CIN', '256'))
-                and getattr(conv, '_spa_packed16', None) is not None):
-            bn_ = 256 if conv.out_channels % 256 == 0 else 128             # the direct kernel's pixel tile (rule below)
-            if -(-x.shape[3] // bn_) * bn_ <= 1.25 * x.shape[3]:
-                wino = None
-        if (wino is not None and x.dtype == torch.float32 and _EPILOGUE['own_conv32']
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and (residual is None or residual.is_contiguous(memory_format=torch.channels_last))):
-            # Winograd: F(4x4,3x3) multiplies 36/144 = 1/4 of the direct form's products and expands the activations
-            # 2.25x (V, M); F(2x2,3x3) 16/36 and 4x.  Executed and direct-equivalent FLOPs are both counted.
-            frac, expand = (0.25, 2.25) if wino[0].shape[0] == 36 else (16.0 / 36.0, 4.0)
-            direct = 2.0 * x.shape[0] * x.shape[2] * x.shape[3] * conv.out_channels * 9 * conv.in_channels
-            _EPILOGUE['wino_direct_flops'] += direct
-            _EPILOGUE['wino_saved_flops'] += direct * (1.0 - frac)
-            px = x.shape[0] * x.shape[2] * x.shape[3]
-            split = wino[0].shape[0] == 36 and _EPILOGUE['split_gemm'] and conv._spa_wino.get('4s')
-            in_bytes = 4.0 * px * (1 + expand) * conv.in_channels            # k_wino_in reads X and writes V
-            mm_bytes = 4.0 * px * expand * (conv.in_channels + conv.out_channels)     # V read, M written
-            out_bytes = 4.0 * px * ((2 if residual is not None else 1) + expand) * conv.out_channels   # M [+ R] read, Y written
-            key = 'gemm' if conv.out_channels % 256 == 0 else 'gemmn'       # the 256 x 256 instance / the narrow tiles
-            if split:
-                key = key.replace('gemm', 'gemm16')
-                if key == 'gemm16':
-                    _EPILOGUE['gemm16_layer_bytes'] += 4.0 * px * (conv.in_channels + (2 if residual is not None else 1) * conv.out_channels) \
-                        + 4.0 * 36 * conv.in_channels * conv.out_channels
-            _EPILOGUE[key + '_flops'] += direct * frac
-            _EPILOGUE[key + '_launches'] += 1
-            _EPILOGUE[key + '_bytes'] += mm_bytes
-            _EPILOGUE['wino_in_bytes'] += in_bytes
-            _EPILOGUE['wino_out_bytes'] += out_bytes
-            _EPILOGUE['wino_launches'] += 1
-            if split:
-                # the bound on max |x| that scales V travels with the tensor object from the call that produced it
-                y, am = eng.conv3x3_wino_f16s(x, split[0], split[1], split[2], residual, relu, conv.dilation[0],
-                                              amax_in=getattr(x, '_spa_amax', None))
-                y._spa_amax = am
-                return y
-            return eng.conv3x3_wino_f32(x, wino[0], wino[1], residual, relu, conv.dilation[0])
-        packed32 = getattr(conv, '_spa_packed32', None)
-        # the direct kernel tiles an image ROW into 256 (128) pixels: on narrow maps most of a tile is padding
-        # (28 pixels at the reference's 224 x 224 operating point: 403 images/s against 2 113 with MIOpen there), so
-        # it is used where a row fills its tiles to 80 % (the Winograd path above flattens the tiles and does not care)
-        if packed32 is not None and not (packed32[0].shape[1] == 1 and getattr(conv, '_spa_packed16', None) is not None
-                                         and _EPILOGUE['split_gemm']):
-            # (the split-plane 1x1 form takes the image as one row: no such limit, engine.conv3x3_f16s)
-            # (... unless the layer is so small that a library convolution's launches cost more than the empty part of the tiles:
-            # the 64-channel layers of a 224 x 224 input; the forward then has no library call left and runs as a captured graph)
-            bn = 256 if conv.out_channels % 256 == 0 else 128
-            if -(-x.shape[3] // bn) * bn > 1.25 * x.shape[3] and x.shape[0] * x.shape[2] * x.shape[3] > (1 << 20):
-                packed32 = None
-        if (packed32 is not None and x.dtype == torch.float32 and _EPILOGUE['own_conv32']
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and (residual is None or residual.is_contiguous(memory_format=torch.channels_last))):
-            # the same layers of the float32 network: libspalign's float32-MFMA implicit GEMM, epilogue fused
-            fl = 2.0 * x.shape[0] * x.shape[2] * x.shape[3] * conv.out_channels * packed32[0].shape[1] * conv.in_channels
-            p16 = getattr(conv, '_spa_packed16', None)
-            if p16 is not None and _EPILOGUE['split_gemm']:
-                # ... on the 16-bit matrix cores at float32 accuracy (two half-precision planes per operand)
-                by = 4.0 * x.shape[0] * x.shape[2] * x.shape[3] * (conv.in_channels + conv.out_channels * (2 if residual is not None else 1))
-                _EPILOGUE['conv16_flops'] += fl
-                _EPILOGUE['conv16_bytes'] += by
-                _EPILOGUE['conv16_launches'] += 1
-                _c16('1x1' if packed32[0].shape[1] == 1 else ('256' if conv.out_channels % 256 == 0 else ('128' if conv.out_channels % 128 == 0 else '64')), fl, by)
-                y, am = eng.conv3x3_f16s(x, p16[0], p16[1], packed32[1], residual, relu, conv.dilation[0],
-                                         amax_in=getattr(x, '_spa_amax', None))
-                y._spa_amax = am
-                return y
-            if packed32[0].shape[1] == 1:           # the GEMM form of the kernel (1x1 projection)
-                key = 'gemm' if conv.out_channels % 256 == 0 and residual is None else 'gemmn'
-                _EPILOGUE[key + '_flops'] += fl
-                _EPILOGUE[key + '_launches'] += 1
-                _EPILOGUE[key + '_bytes'] += 4.0 * x.shape[0] * x.shape[2] * x.shape[3] * (conv.in_channels + conv.out_channels)
-            else:
-                _EPILOGUE['conv_flops'] += fl
-            return eng.conv3x3_f32(x, packed32[0], packed32[1], residual, relu, conv.dilation[0])
-        l2 = getattr(conv, '_spa_layer2', None)
-        if (l2 is not None and _EPILOGUE['split_gemm'] and _EPILOGUE['own_conv32'] and x.dtype == torch.float32 and relu
-                and residual is None and x.is_contiguous(memory_format=torch.channels_last)):
-            # layer 2 of arch D (16 -> 32 channels, stride 2): its own kernel on the 16-bit matrix cores
-            fl2 = 2.0 * x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2) * 32 * 9 * 16
-            by2 = 4.0 * x.shape[0] * (x.shape[2] * x.shape[3] * 16 + ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2) * 32)
-            _EPILOGUE['conv16_flops'] += fl2
-            _EPILOGUE['conv16_bytes'] += by2
-            _EPILOGUE['conv16_launches'] += 1
-            _c16('front', fl2, by2)
-            return eng.drn_layer2_f16s(x, l2[0], l2[1], l2[2], amax_in=getattr(x, '_spa_amax', None))
-        l232 = getattr(conv, '_spa_layer2_32', None)
-        if (l232 is not None and not _EPILOGUE['split_gemm'] and _EPILOGUE['own_conv32'] and x.dtype == torch.float32 and relu
-                and residual is None and x.is_contiguous(memory_format=torch.channels_last)):
-            # the strict float32 network (float32 instructions everywhere): layer 2 as fmaf chains on the vector pipe
-            _EPILOGUE['conv_flops'] += 2.0 * x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2) * 32 * 9 * 16
-            return eng.drn_layer2_f32(x, l232[0], l232[1])
-        _EPILOGUE['library_convs'] += 1               # (MIOpen picks its algorithm per call context: such a forward is not captured)
-        if os.environ.get('SPA_DRN_TRACE_LIBRARY'):
-            import sys
-            sys.stderr.write('[drn] library convolution: %d -> %d, kernel %s stride %s dilation %s on %s %s\n' % (
-                conv.in_channels, conv.out_channels, tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.dilation), tuple(x.shape), x.dtype))
-        y = F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation)
-        vec = 4 if y.dtype == torch.float32 else 8
-        if (y.is_contiguous(memory_format=torch.channels_last) and y.shape[1] % vec == 0
-                and (residual is None or residual.is_contiguous(memory_format=torch.channels_last))):
-            _EPILOGUE['bytes'] += y.numel() * y.element_size() * (3 if residual is not None else 2)
-            _EPILOGUE['launches'] += 1
-            return eng.bias_act_(y, conv.bias, residual, relu, track_amax=_EPILOGUE['split_gemm'])
-        y = y + conv.bias.view(1, -1, 1, 1)
-    else:
-        _EPILOGUE['library_convs'] += 1
-        y = bn(conv(x))
+# ---- the dispatch of a convolution, a block and a chunk: CHOOSE a route from plain values (no tensor work, no side effect),
+# COUNT its FLOPs and bytes into _EPILOGUE (bench.py's roofline rows), LAUNCH the Engine call -------------------------------
+F32, BF16 = torch.float32, torch.bfloat16
+# what a choice reads from outside its call (debug: spa_debug_set keys 1, 3, 4 of the engine, None without one)
+Flags = collections.namedtuple('Flags', 'split_gemm own_conv own_conv32 winograd bf16_light wino_min_cin debug')
+# a layer's static facts; folded: BatchNorm folded into its bias; families: the operands prepare() packed for it
+Layer = collections.namedtuple('Layer', 'cin cout k stride dilation folded families')
+# a call's facts; gpu: an engine and the tensor on the GPU; layout: x and the residual in channels-last storage
+Call = collections.namedtuple('Call', 'dtype B H W gpu layout residual relu')
+
+
+def _flags():
+    """Read at EVERY call (the switches are live: bench.py and the tests flip them on prepared models); _graph_forward's key is
+    built from the same tuple."""
+    E, eng = _EPILOGUE, _EPILOGUE['engine']
+    return Flags(E['split_gemm'], E['own_conv'], E['own_conv32'], E['winograd'], os.environ.get('SPA_BF16_LIGHT', '1') != '0',
+                 int(os.environ.get('SPA_WINO_MIN_CIN', '256')),
+                 None if eng is None else (eng.debug_get(1, 1), eng.debug_get(3, 1), eng.debug_get(4, 2)))
+
+
+def _nhwc(*tensors):
+    """the layout every libspalign kernel wants of its input and (where there is one) of the residual"""
+    return all(t is None or t.is_contiguous(memory_format=torch.channels_last) for t in tensors)
+
+
+def _layer(conv, bn, holder=None):
+    return Layer(conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.stride[0], conv.dilation[0],
+                 isinstance(bn, nn.Identity) and conv.bias is not None, tuple(getattr(holder or conv, '_spa_ops', ())))
+
+
+def _call(x, residual, relu):
+    return Call(x.dtype, x.shape[0], x.shape[2], x.shape[3], _EPILOGUE['engine'] is not None and x.is_cuda, _nhwc(x, residual),
+                residual is not None, relu)
+
+
+def _row_fills(W, bn):
+    """The direct kernels tile an image ROW into `bn` pixels: on narrow maps most of a tile is padding (28 pixels at the
+    reference's 224 x 224 operating point: 403 images/s against 2 113 with MIOpen there).  True where a row fills its tiles to
+    80 % (the Winograd kernels flatten the tiles, the split-plane 1x1 form takes the image as one row: neither cares)."""
+    return -(-W // bn) * bn <= 1.25 * W
+
+
+def _out(n, stride):
+    return -(-n // stride)
+
+
+def choose_conv(L, c, f):
+    """The route of relu?(conv(x) + bias [+ residual]): one of _CONV's names."""
+    if not (c.gpu and L.folded and c.dtype in (F32, BF16)):
+        return 'torch'
+    fam = L.families
+    f32, b16 = c.dtype == F32 and f.own_conv32 and c.layout, c.dtype == BF16 and f.own_conv and c.layout
+    if b16 and 'bf16' in fam:
+        return 'bf16'
+    if b16 and 'light' in fam and f.bf16_light:
+        return 'bf16_light'
+    bn = 256 if L.cout % 256 == 0 else 128                  # the direct kernel's pixel tile
+    wino = ('wino4' if f.winograd == 4 else 'wino2') if f.winograd else None           # 4 (default), 2 or 0 / False
+    # with the split-plane kernels the direct form wins below 256 input channels (30 x 128 x 256 pixels, ms Winograd /
+    # direct: 128 -> 128 1.10 / 0.99, 128 -> 256 1.85 / 1.61, 256 -> 256 2.65 / 3.09, 256 -> 512 4.28 / 5.35)
+    if f32 and wino in fam and not (f.split_gemm and L.cin < f.wino_min_cin and 'direct' in fam and _row_fills(c.W, bn)):
+        return 'wino4_f16s' if wino == 'wino4' and f.split_gemm and 'wino4s' in fam else wino + '_f32'
+    # (a layer so small that a library convolution's launches cost more than the empty part of the tiles stays direct: the
+    # 64-channel layers of a 224 x 224 input; the forward then has no library call left and runs as a captured graph)
+    if f32 and 'direct' in fam and (L.k == 1 and f.split_gemm or _row_fills(c.W, bn) or c.B * c.H * c.W <= 1 << 20):
+        return ('direct%d_f16s' if f.split_gemm else 'direct%d_f32') % L.k
+    if f32 and 'layer2' in fam and c.relu and not c.residual:
+        return 'layer2_f16s' if f.split_gemm else 'layer2_f32'
+    return 'library'
+
+
+def choose_block(L, c, f):
+    """L: the block's opening convolution, with family 's2' where prepare() packed it together with the projection."""
+    if 's2' in L.families and c.gpu and c.dtype == F32 and f.own_conv32 and c.layout:
+        if not f.split_gemm:
+            return 's2_f32'
+        # (narrow maps — 224 x 224 inputs — leave most of a 128-pixel tile empty; the layer is then so small that this costs
+        # less than a library convolution and its epilogue pass, and the forward stays capturable)
+        if _row_fills(_out(c.W, 2), 128) or c.B * _out(c.H, 2) * _out(c.W, 2) <= 1 << 20:
+            return 's2_f16s'
+    return 'separate'
+
+
+def choose_chunk(families, fused, dtype, gpu, f):
+    """families: which of the model's front operands ('_front_c', '_stem_c16', '_stem') prepare() packed."""
+    if not gpu:
+        return 'host'
+    if fused and '_front_c' in families and f.split_gemm and f.own_conv32 and dtype == F32:
+        return 'front_c'
+    if fused and '_stem_c16' in families and f.own_conv and dtype == BF16:
+        return 'stem_c16'
+    return 'stem_d' if fused and '_stem' in families else 'normalise'
+
+
+def _flops(px, cout, taps, cin):
+    """2 * MACs of a convolution with `px` output pixels"""
+    return 2.0 * px * cout * taps * cin
+
+
+def _work(L, c, proj=0):
+    """-> (input pixels, output pixels, 2 * MACs, tensors of the output's size read or written).  proj = 1: a stride-2 opener
+    with the block's 1x1 projection in the same pass (a tenth tap, a second output)."""
+    opx = c.B * _out(c.H, L.stride) * _out(c.W, L.stride)
+    return c.B * c.H * c.W, opx, _flops(opx, L.cout, L.k * L.k + proj, L.cin), (2 if c.residual else 1) + proj
+
+
+def _add(prefix, flops, nbytes, launches=1):
+    _EPILOGUE[prefix + '_flops'] += flops
+    _EPILOGUE[prefix + '_bytes'] += nbytes
+    _EPILOGUE[prefix + '_launches'] += launches
+
+
+def _add16(kind, flops, nbytes, launches=1):
+    """the split-plane direct kernels (16-bit matrix cores at float32 accuracy): in all and per instantiation"""
+    _add('conv16', flops, nbytes, launches)
+    _c16(kind, flops, nbytes, launches)
+
+
+def _count_flops(L, c, proj=0):
+    _EPILOGUE['conv_flops'] += _work(L, c, proj)[2]
+
+
+def _count_light(L, c):
+    px, opx, flops, nout = _work(L, c)
+    _add('light', flops, 2.0 * (px * L.cin + opx * L.cout * nout))
+
+
+def _count_f16s(L, c, kind=None, proj=0):
+    px, opx, flops, nout = _work(L, c, proj)
+    _add16(kind or ('256' if L.cout % 256 == 0 else ('128' if L.cout % 128 == 0 else '64')), flops, 4.0 * (px * L.cin + opx * L.cout * nout))
+
+
+def _count_gemm1(L, c):
+    px, _, flops, _ = _work(L, c)
+    _add('gemm' if L.cout % 256 == 0 and not c.residual else 'gemmn', flops, 4.0 * px * (L.cin + L.cout))
+
+
+def _count_wino(L, c, frac, expand, split):
+    """Winograd: F(4x4,3x3) multiplies 36/144 = 1/4 of the direct form's products and expands the activations 2.25x (V, M);
+    F(2x2,3x3) 16/36 and 4x.  Executed and direct-equivalent FLOPs are both counted."""
+    E, (px, _, direct, nout) = _EPILOGUE, _work(L, c)
+    E['wino_direct_flops'] += direct
+    E['wino_saved_flops'] += direct * (1.0 - frac)
+    wide = L.cout % 256 == 0                                  # the 256 x 256 instance / the narrow tiles
+    if split and wide:
+        E['gemm16_layer_bytes'] += 4.0 * px * (L.cin + nout * L.cout) + 4.0 * 36 * L.cin * L.cout
+    _add(('gemm16' if split else 'gemm') + ('' if wide else 'n'), direct * frac, 4.0 * px * expand * (L.cin + L.cout))  # V read, M written
+    E['wino_in_bytes'] += 4.0 * px * (1 + expand) * L.cin                         # k_wino_in reads X and writes V
+    E['wino_out_bytes'] += 4.0 * px * (nout + expand) * L.cout                    # M [+ R] read, Y written
+    E['wino_launches'] += 1
+
+
+def _count_library(L, c):
+    _EPILOGUE['library_convs'] += 1               # (MIOpen picks its algorithm per call context: such a forward is not captured)
+
+
+def _amax_on(y, am):
+    """the bound on max |y| that scales the next layer's planes travels with the tensor object (in: amax_in=_amax_of(x))"""
+    y._spa_amax = am
+    return y
+
+
+def _amax_of(x):
+    return getattr(x, '_spa_amax', None)
+
+
+def _launch_library(eng, conv, x, residual, relu):
+    if os.environ.get('SPA_DRN_TRACE_LIBRARY'):
+        import sys
+        sys.stderr.write('[drn] library convolution: %d -> %d, kernel %s stride %s dilation %s on %s %s\n' % (
+            conv.in_channels, conv.out_channels, tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.dilation), tuple(x.shape), x.dtype))
+    return _bias_act(eng, conv, F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation), residual, relu)
+
+
+def _count_bias_act(nbytes):
+    _EPILOGUE['bytes'] += nbytes                  # read y + write y [+ read residual]
+    _EPILOGUE['launches'] += 1
+
+
+def _bias_act(eng, conv, y, residual, relu):
+    """Behind a library convolution, dispatched by the layout the library gave y: libspalign's bias / residual / ReLU as ONE
+    in-place pass instead of two or three elementwise kernels."""
+    if not (_nhwc(y, residual) and y.shape[1] % (4 if y.dtype == F32 else 8) == 0):
+        return _torch_epilogue(y + conv.bias.view(1, -1, 1, 1), residual, relu)
+    _count_bias_act(y.numel() * y.element_size() * (3 if residual is not None else 2))
+    return eng.bias_act_(y, conv.bias, residual, relu, track_amax=_EPILOGUE['split_gemm'])
+
+
+def _torch_epilogue(y, residual, relu):
     if residual is not None:
         y = y + residual
     return F.relu_(y) if relu else y
+
+
+def _launch(method, family, amax=False):
+    """eng.method(x, *the family's operands, residual, relu, dilation); amax: a split-plane kernel, which takes the bound on
+    max |x| and returns (y, the bound on max |y|)"""
+    def launch(eng, m, x, res, relu):
+        if not amax:
+            return getattr(eng, method)(x, *m._spa_ops[family], res, relu, m.dilation[0])
+        return _amax_on(*getattr(eng, method)(x, *m._spa_ops[family], res, relu, m.dilation[0], amax_in=_amax_of(x)))
+    return launch
+
+
+# route: (count(L, c), launch(eng, conv, x, residual, relu))
+_CONV = {
+    # the bf16 network: the heavy 3x3 stride-1 layers from 64 channels up / the rest (stride 2, 16 / 32 channels, 1x1 projections)
+    'bf16': (_count_flops, _launch('conv3x3_bf16', 'bf16')),
+    'bf16_light': (_count_light, lambda eng, m, x, res, relu: eng.conv_bf16_light(x, *m._spa_ops['light'], res, relu, m.stride[0], m.dilation[0])),
+    # Winograd F(4x4,3x3) on split half-precision planes; F(4x4) and F(2x2) with float32 matrix instructions
+    'wino4_f16s': (partial(_count_wino, frac=0.25, expand=2.25, split=True), _launch('conv3x3_wino_f16s', 'wino4s', amax=True)),
+    'wino4_f32': (partial(_count_wino, frac=0.25, expand=2.25, split=False), _launch('conv3x3_wino_f32', 'wino4')),
+    'wino2_f32': (partial(_count_wino, frac=16.0 / 36.0, expand=4.0, split=False), _launch('conv3x3_wino_f32', 'wino2')),
+    # the direct implicit GEMM, 3x3 and (centre tap only) 1x1: on split planes / with float32 matrix instructions (whose 1x1
+    # form is counted with the GEMMs)
+    'direct3_f16s': (_count_f16s, _launch('conv3x3_f16s', 'direct_s', amax=True)),
+    'direct1_f16s': (partial(_count_f16s, kind='1x1'), _launch('conv3x3_f16s', 'direct_s', amax=True)),
+    'direct3_f32': (_count_flops, _launch('conv3x3_f32', 'direct')),
+    'direct1_f32': (_count_gemm1, _launch('conv3x3_f32', 'direct')),
+    # layer 2 of arch D (16 -> 32 channels, stride 2): on split planes / as fmaf chains on the vector pipe
+    'layer2_f16s': (partial(_count_f16s, kind='front'), lambda eng, m, x, res, relu: eng.drn_layer2_f16s(x, *m._spa_ops['layer2_s'], amax_in=_amax_of(x))),
+    'layer2_f32': (_count_flops, lambda eng, m, x, res, relu: eng.drn_layer2_f32(x, *m._spa_ops['layer2'])),
+    'library': (_count_library, _launch_library),                        # MIOpen, then libspalign's bias_act_
+}
+
+
+def _launch_s2_f16s(eng, blk, x):
+    y, res, am = eng.conv3x3_s2_f16s(x, *blk._spa_ops['s2_s'], True, amax_in=_amax_of(x))
+    return _amax_on(y, am), res
+
+
+# a block's stride-2 opening convolution and its 1x1 stride-2 projection in ONE pass over x (csrc/spa_conv32.hip):
+# route: (count(L, c), launch(eng, block, x) -> (y, the projected residual))
+_BLOCK = {'s2_f16s': (partial(_count_f16s, kind='front', proj=1), _launch_s2_f16s),
+          's2_f32': (partial(_count_flops, proj=1), lambda eng, blk, x: eng.conv3x3_s2_f32(x, *blk._spa_ops['s2'], True))}
+
+
+def conv_bias_act(conv, bn, x, residual=None, relu=True):
+    """relu?(bn(conv(x)) [+ residual]).  With BatchNorm folded (bn is Identity, conv carries the bias) and the tensors on the
+    GPU in channels-last storage this is ONE libspalign kernel with bias, residual and ReLU in its epilogue; the layers no
+    kernel takes go to the library's convolution with libspalign's fused epilogue pass behind it."""
+    L, c = _layer(conv, bn), _call(x, residual, relu)
+    route = choose_conv(L, c, _flags())
+    if route == 'torch':
+        _EPILOGUE['library_convs'] += 1
+        return _torch_epilogue(bn(conv(x)), residual, relu)
+    count, launch = _CONV[route]
+    count(L, c)
+    return launch(_EPILOGUE['engine'], conv, x, residual, relu)
 
 
 class BasicBlock(nn.Module):
@@ -291,38 +400,141 @@ class BasicBlock(nn.Module):
         self.residual = residual
 
     def forward(self, x):
-        s2 = getattr(self, '_spa_s2', None)
-        eng = _EPILOGUE['engine']
-        if (s2 is not None and eng is not None and _EPILOGUE['split_gemm'] and _EPILOGUE['own_conv32'] and x.is_cuda
-                and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
-                and (128 * -(-((x.shape[3] + 1) // 2) // 128) <= 1.25 * ((x.shape[3] + 1) // 2)
-                     # (narrow maps — 224 x 224 inputs, the reference's operating point — leave most of a 128-pixel tile empty; the
-                     # layer is then so small that this costs less than the launches of a library convolution and its epilogue
-                     # pass, and the forward stays on libspalign's kernels, which is what lets it run as a captured graph)
-                     or x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2) <= (1 << 20))):
-            # the stride-2 opening convolution and the 1x1 stride-2 projection in ONE pass over x (csrc/spa_conv32.hip)
-            fl2 = 2.0 * x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2) * s2[3] * 10 * x.shape[1]
-            by2 = 4.0 * x.shape[0] * (x.shape[2] * x.shape[3] * x.shape[1] + ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2) * 2 * s2[3])
-            _EPILOGUE['conv16_flops'] += fl2
-            _EPILOGUE['conv16_bytes'] += by2
-            _EPILOGUE['conv16_launches'] += 1
-            _c16('front', fl2, by2)
-            y, res, am = eng.conv3x3_s2_f16s(x, s2[0], s2[1], s2[2], s2[3], True, amax_in=getattr(x, '_spa_amax', None))
-            y._spa_amax = am
-            return conv_bias_act(self.conv2, self.bn2, y, res, True)
-        s232 = getattr(self, '_spa_s2_32', None)
-        if (s232 is not None and eng is not None and not _EPILOGUE['split_gemm'] and _EPILOGUE['own_conv32'] and x.is_cuda
-                and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
-            # the strict float32 network: the same one-pass opener + projection with float32 matrix instructions
-            _EPILOGUE['conv_flops'] += 2.0 * x.shape[0] * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2) * s232[2] * 10 * x.shape[1]
-            y, res = eng.conv3x3_s2_f32(x, s232[0], s232[1], s232[2], True)
-            return conv_bias_act(self.conv2, self.bn2, y, res, True)
-        y = conv_bias_act(self.conv1, self.bn1, x, None, True)
-        res = None
-        if self.residual:
-            res = x if self.downsample is None else conv_bias_act(self.downsample[0], self.downsample[1],
-                                                                  x, None, False)
+        L, c = _layer(self.conv1, self.bn1, self), _call(x, None, True)
+        route = choose_block(L, c, _flags())
+        if route == 'separate':
+            y = conv_bias_act(self.conv1, self.bn1, x, None, True)
+            res = None
+            if self.residual:
+                res = x if self.downsample is None else conv_bias_act(self.downsample[0], self.downsample[1], x, None, False)
+        else:
+            count, launch = _BLOCK[route]
+            count(L, c)
+            y, res = launch(_EPILOGUE['engine'], self, x)
         return conv_bias_act(self.conv2, self.bn2, y, res, True)
+
+
+def _count_front_c(B, _, H, W):
+    """layer1's two 16 -> 16 convolutions at full resolution (the first inside the stem kernel, whose 7x7 is not counted), layer2's
+    opener 16 -> 32 with its projection and its second convolution 32 -> 32 at half: three launches behind the stem's"""
+    px, opx = B * H * W, B * _out(H, 2) * _out(W, 2)
+    _add16('front', _flops(px, 16, 9, 16) + _flops(opx, 32, 9 + 1, 16) + _flops(opx, 32, 9, 32),
+           4.0 * (px * (16 + 16 + 16) + px * 16 + opx * (32 + 32) + opx * (32 + 32 + 32)), 3)
+
+
+def _launch_front_c(model, eng, xc):
+    """DRN-C: conv1 .. layer2 on libspalign's kernels (no MIOpen convolution, no separate epilogue pass)"""
+    fc = model._front_c
+    a1, y0 = eng.drn_stem_d(xc.float().contiguous(), *fc['stem'], dtype=F32, split=True, want_layer0=True)
+    l1, _ = eng.conv_small_f16s(a1, *fc['l1c2'], 16, 1, 0, y0, True, amax_in=a1._spa_amax)
+    a2, proj = eng.conv_small_f16s(l1, *fc['l2c1'], 32, 2, 32, None, True, amax_in=l1._spa_amax)
+    l2, _ = eng.conv_small_f16s(a2, *fc['l2c2'], 32, 1, 0, proj, True, amax_in=a2._spa_amax)
+    return model.forward_maps(None, front_maps=[l1, l2])
+
+
+def _launch_stem_c16(model, eng, xc):
+    a1, y0 = eng.drn_stem_d(xc.float().contiguous(), *model._stem_c16, dtype=BF16, want_layer0=True)
+    b1 = model.layer1[0]
+    return model.forward_maps(None, front_maps=[conv_bias_act(b1.conv2, b1.bn2, a1, y0, True)])
+
+
+def _launch_host(model, eng, xc):
+    xi = model.normalise(xc.float())
+    return model.forward(xi.to(model.compute_dtype).contiguous(memory_format=torch.channels_last))[1]
+
+
+# route: (count(B, 3, H, W) or None, launch(model, eng, raw sub-batch) -> the 8 maps)
+_CHUNK = {
+    'front_c': (_count_front_c, _launch_front_c),
+    'stem_c16': (None, _launch_stem_c16),
+    'stem_d': (None, lambda model, eng, xc: model.forward_maps(None, layer1_out=eng.drn_stem_d(
+        xc.float().contiguous(), *model._stem, dtype=model.compute_dtype, split=_EPILOGUE['split_gemm'] and model.compute_dtype == F32))),
+    'normalise': (None, lambda model, eng, xc: model.forward(eng.drn_normalise(xc.float().contiguous(), model.compute_dtype))[1]),
+    'host': (None, _launch_host),
+}
+
+
+# ---- what prepare() packs: eligibility is a pure predicate of the layer and the network's dtype ----------------------------
+def conv_families(m, dtype, folded):
+    """The operand families of convolution `m` in a network of `dtype`.  Winograd where it wins (measured, 30 x 128 x 256
+    pixels, ms direct / F(2x2) / F(4x4)):
+      512 -> 512  33.2 / 19.8 / 11.9     256 -> 512  16.8 / 11.6 / 7.0     256 -> 256  8.5 / 6.6 / 4.2
+      128 -> 256   4.3 /  4.1 /  2.6     128 -> 128   2.4 /  2.4 / 1.6      64 -> 64 (256 x 512)  2.6 / - / 2.7
+    so F(4x4,3x3) from 128 input channels up and F(2x2,3x3) (kept as an option) from 256."""
+    if not (folded and m.groups == 1 and m.bias is not None and dtype in (F32, BF16)):
+        return ()
+    k, s, d, pad, ci, co = m.kernel_size, m.stride, m.dilation, m.padding, m.in_channels, m.out_channels
+    same3 = k == (3, 3) and pad == d and d[0] == d[1]                  # 3x3, padding = dilation
+    one = k == (1, 1) and pad == (0, 0)
+    fam = []
+    if dtype == F32:
+        if same3 and s == (2, 2) and d == (1, 1) and ci == 16 and co == 32:
+            fam += ['layer2', 'layer2_s']                             # layer 2 of arch D (_s: as split half-precision planes)
+        if same3 and s == (1, 1) and ci % 32 == 0 and co % 64 == 0 and ci >= 128 and co >= 128:
+            fam.append('wino4')
+            if co % 128 == 0:
+                fam.append('wino4s')                                  # ... as split half-precision planes
+            if ci >= 256 and co >= 256:
+                fam.append('wino2')
+        # spa_conv3x3_f32 / _f16s: the 3x3 stride-1 layers from 64 channels up, and the 1x1 stride-1 projections (layers 5, 6)
+        # through the same kernel, centre tap only
+        if (same3 and d[0] <= 4 or one) and s == (1, 1) and ci % 32 == 0 and co % 64 == 0:
+            fam += ['direct', 'direct_s']
+    elif same3 and s == (1, 1) and d[0] <= 4 and ci % 64 == 0 and co % 64 == 0:
+        fam.append('bf16')                                            # spa_conv3x3_bf16: layers 3-8 of the DRN
+    elif (s in ((1, 1), (2, 2)) and (same3 and ci in (16, 32, 64) or one and ci in (16, 32, 64, 128, 256))
+          and (co % 64 == 0 and ci >= 32 or co % 32 == 0 and ci <= 32 or co % 16 == 0 and ci == 16)):
+        fam.append('light')                                           # spa_conv_bf16_light: every other convolution
+    return tuple(fam)
+
+
+def _pack_conv(m, fam, Engine):
+    """{family: operands}; bias float32, weights as (n, tap, c)"""
+    if not fam:
+        return {}
+    ops, bias = {}, m.bias.detach().float().contiguous()
+    wt = m.weight.detach().permute(0, 2, 3, 1).reshape(m.out_channels, -1, m.in_channels).contiguous()
+    if 'layer2' in fam:     # (the strict float32 network's form: (tap, input channel, output channel) float32)
+        ops['layer2'] = (m.weight.detach().float().permute(2, 3, 1, 0).reshape(9, 16, 32).contiguous(), bias)
+        ops['layer2_s'] = Engine.layer2_planes(m.weight) + (bias,)
+    for name, tile in (('wino4', 4), ('wino2', 2)):
+        if name in fam:
+            ops[name] = (Engine.winograd_weights(m.weight, tile), bias)
+    if 'wino4s' in fam:
+        ops['wino4s'] = Engine.winograd_weights_split(m.weight) + (bias,)
+    if 'direct' in fam:
+        ops['direct'] = (wt.float(), bias)
+        ops['direct_s'] = Engine.split_planes(wt.float()) + (bias,)
+    if 'bf16' in fam or 'light' in fam:
+        ops[fam[0]] = (wt.to(BF16), bias)
+    return ops
+
+
+def block_families(blk, dtype, folded):
+    c1, ds = blk.conv1, blk.downsample
+    return ('s2', 's2_s') if (dtype == F32 and folded and blk.residual and ds is not None and c1.stride == (2, 2)
+                               and c1.kernel_size == (3, 3) and c1.padding == (1, 1) and c1.dilation == (1, 1) and c1.bias is not None
+                               and ds[0].kernel_size == (1, 1) and ds[0].stride == (2, 2) and ds[0].bias is not None
+                               and c1.in_channels % 32 == 0 and c1.out_channels % 64 == 0) else ()
+
+
+def _pack_block(blk, fam, Engine):
+    """the opener's and (centre tap) the projection's weights as one (2 Cout, 9, Cin) convolution, both biases, Cout"""
+    if not fam:
+        return {}
+    c1, ds = blk.conv1, blk.downsample
+    co, ci = c1.out_channels, c1.in_channels
+    w = torch.zeros((2 * co, 9, ci), dtype=F32, device=c1.weight.device)
+    w[:co] = c1.weight.detach().float().permute(0, 2, 3, 1).reshape(co, 9, ci)
+    w[co:, 4] = ds[0].weight.detach().float().reshape(co, ci)
+    bias = torch.cat([c1.bias.detach().float(), ds[0].bias.detach().float()]).contiguous()
+    return {'s2': (w.contiguous(), bias, co), 's2_s': Engine.split_planes(w) + (bias, co)}
+
+
+def _pack_stem(c0, c1):
+    """operands of the fused stem kernels: the 7x7 and the first 3x3 convolution, weights as (n, ky kx c)"""
+    return (c0.weight.detach().float().reshape(16, 147).contiguous(), c0.bias.detach().float().contiguous(),
+            c1.weight.detach().float().permute(0, 2, 3, 1).reshape(16, 144).contiguous(), c1.bias.detach().float().contiguous())
 
 
 class DRN(nn.Module):
@@ -427,119 +639,28 @@ class DRN(nn.Module):
             _EPILOGUE['engine'] = default_engine()
             for m in self.modules():
                 if isinstance(m, nn.Conv2d):
-                    m._spa_packed = None
-                    m._spa_packed32 = None
-                    m._spa_packed16 = None
-                    m._spa_layer2 = None
-                    m._spa_layer2_32 = None
-                    if (dtype == torch.float32 and self.folded and m.kernel_size == (3, 3) and m.stride == (2, 2)
-                            and m.padding == (1, 1) and m.dilation == (1, 1) and m.groups == 1 and m.in_channels == 16
-                            and m.out_channels == 32 and m.bias is not None):
-                        m._spa_layer2 = Engine.layer2_planes(m.weight) + (m.bias.detach().float().contiguous(),)
-                        # (the strict float32 network's form: (tap, input channel, output channel) float32)
-                        m._spa_layer2_32 = (m.weight.detach().float().permute(2, 3, 1, 0).reshape(9, 16, 32).contiguous(),
-                                            m.bias.detach().float().contiguous())
-                    m._spa_wino = {}
-                    # Winograd where it wins (measured, 30 x 128 x 256 pixels, ms direct / F(2x2) / F(4x4)):
-                    #   512 -> 512  33.2 / 19.8 / 11.9     256 -> 512  16.8 / 11.6 / 7.0     256 -> 256  8.5 / 6.6 / 4.2
-                    #   128 -> 256   4.3 /  4.1 /  2.6     128 -> 128   2.4 /  2.4 / 1.6      64 -> 64 (256 x 512)  2.6 / - / 2.7
-                    # F(4x4,3x3) from 128 input channels up, F(2x2,3x3) (kept as an option) from 256
-                    if (dtype == torch.float32 and self.folded and m.kernel_size == (3, 3) and m.stride == (1, 1)
-                            and m.padding == m.dilation and m.dilation[0] == m.dilation[1] and m.groups == 1
-                            and m.in_channels % 32 == 0 and m.out_channels % 64 == 0 and m.bias is not None
-                            and m.in_channels >= 128 and m.out_channels >= 128):
-                        bias32 = m.bias.detach().float().contiguous()
-                        m._spa_wino[4] = (Engine.winograd_weights(m.weight, 4), bias32)
-                        if m.out_channels % 128 == 0:
-                            m._spa_wino['4s'] = Engine.winograd_weights_split(m.weight) + (bias32,)
-                        if m.in_channels >= 256 and m.out_channels >= 256:
-                            m._spa_wino[2] = (Engine.winograd_weights(m.weight, 2), bias32)
-                    # operands of spa_conv3x3_f32: the same layers of the float32 network (Cin % 32 == 0)
-                    if (dtype == torch.float32 and self.folded and m.kernel_size == (3, 3) and m.stride == (1, 1)
-                            and m.padding == m.dilation and m.dilation[0] == m.dilation[1] <= 4 and m.groups == 1
-                            and m.in_channels % 32 == 0 and m.out_channels % 64 == 0 and m.bias is not None):
-                        wt = m.weight.detach().permute(0, 2, 3, 1).reshape(m.out_channels, 9, m.in_channels)
-                        m._spa_packed32 = (wt.contiguous().float(), m.bias.detach().float().contiguous())
-                        m._spa_packed16 = Engine.split_planes(m._spa_packed32[0])
-                    # ... and the 1x1 stride-1 projections (layers 5 and 6): the same kernel, centre tap only
-                    if (dtype == torch.float32 and self.folded and m.kernel_size == (1, 1) and m.stride == (1, 1)
-                            and m.padding == (0, 0) and m.groups == 1 and m.in_channels % 32 == 0
-                            and m.out_channels % 64 == 0 and m.bias is not None):
-                        wt = m.weight.detach().reshape(m.out_channels, 1, m.in_channels)
-                        m._spa_packed32 = (wt.contiguous().float(), m.bias.detach().float().contiguous())
-                        m._spa_packed16 = Engine.split_planes(m._spa_packed32[0])
-                    # operands of spa_conv3x3_bf16: 3x3, stride 1, padding = dilation, Cin % 64 == 0,
-                    # Cout % 64 == 0 (layers 3-8 of the DRN: all 3x3 stride-1 layers from 64 channels up), bf16 network,
-                    # BatchNorm folded
-                    if (dtype == torch.bfloat16 and self.folded and m.kernel_size == (3, 3) and m.stride == (1, 1)
-                            and m.padding == m.dilation and m.dilation[0] == m.dilation[1] <= 4 and m.groups == 1
-                            and m.in_channels % 64 == 0 and m.out_channels % 64 == 0 and m.bias is not None):
-                        wt = m.weight.detach().permute(0, 2, 3, 1).reshape(m.out_channels, 9, m.in_channels)
-                        m._spa_packed = (wt.contiguous().to(torch.bfloat16), m.bias.detach().float().contiguous())
-                    # operands of spa_conv_bf16_light: every other convolution of the bf16 network (stride 2, 16 / 32 input
-                    # channels, 1x1 projections)
-                    m._spa_light = None
-                    if (dtype == torch.bfloat16 and self.folded and getattr(m, '_spa_packed', None) is None and m.groups == 1
-                            and m.bias is not None and m.stride in ((1, 1), (2, 2))
-                            and ((m.kernel_size == (3, 3) and m.padding == m.dilation and m.dilation[0] == m.dilation[1]
-                                  and m.in_channels in (16, 32, 64))
-                                 or (m.kernel_size == (1, 1) and m.padding == (0, 0) and m.in_channels in (16, 32, 64, 128, 256)))
-                            and (m.out_channels % 64 == 0 and m.in_channels >= 32 or m.out_channels % 32 == 0 and m.in_channels <= 32
-                                 or m.out_channels % 16 == 0 and m.in_channels == 16)):
-                        taps = m.kernel_size[0] * m.kernel_size[1]
-                        wt = m.weight.detach().permute(0, 2, 3, 1).reshape(m.out_channels, taps, m.in_channels)
-                        m._spa_light = (wt.contiguous().to(torch.bfloat16), m.bias.detach().float().contiguous())
-            for blk in self.modules():
-                if isinstance(blk, BasicBlock):
-                    blk._spa_s2 = None
-                    blk._spa_s2_32 = None
-                    c1, ds = blk.conv1, blk.downsample
-                    if (dtype == torch.float32 and self.folded and blk.residual and ds is not None and c1.stride == (2, 2)
-                            and c1.kernel_size == (3, 3) and c1.padding == (1, 1) and c1.dilation == (1, 1) and c1.bias is not None
-                            and ds[0].kernel_size == (1, 1) and ds[0].stride == (2, 2) and ds[0].bias is not None
-                            and c1.in_channels % 32 == 0 and c1.out_channels % 64 == 0):
-                        co, ci = c1.out_channels, c1.in_channels
-                        w = torch.zeros((2 * co, 9, ci), dtype=torch.float32, device=c1.weight.device)
-                        w[:co] = c1.weight.detach().float().permute(0, 2, 3, 1).reshape(co, 9, ci)
-                        w[co:, 4] = ds[0].weight.detach().float().reshape(co, ci)
-                        wt2, inv_t = Engine.split_planes(w)
-                        blk._spa_s2 = (wt2, inv_t, torch.cat([c1.bias.detach().float(), ds[0].bias.detach().float()]).contiguous(), co)
-                        blk._spa_s2_32 = (w.contiguous(), blk._spa_s2[2], co)      # the strict float32 network's operands
+                    m._spa_ops = _pack_conv(m, conv_families(m, dtype, self.folded), Engine)
+                elif isinstance(m, BasicBlock):
+                    m._spa_ops = _pack_block(m, block_families(m, dtype, self.folded), Engine)
+            fam = self.front_families(dtype)
+            f32 = lambda t: t.detach().float().contiguous()
             self._front_c = None
-            if self.arch == 'C' and self.folded and dtype == torch.float32:
+            if '_front_c' in fam:
                 # DRN-C's full-resolution front on libspalign's own kernels (csrc/spa_stem.hip, spa_convs.hip): conv1 + layer1's first
                 # convolution as the fused stem (which also stores conv1's output, the block's residual), layer1's second convolution,
                 # layer2's stride-2 opener together with its 1x1 projection, layer2's second convolution
                 c0, b1, b2 = self.conv1, self.layer1[0], self.layer2[0]
-                ok = (len(self.layer1) == 1 and len(self.layer2) == 1 and b1.residual and b1.downsample is None and b2.residual
-                      and b2.downsample is not None and b2.conv1.stride == (2, 2) and b2.downsample[0].stride == (2, 2)
-                      and all(c.bias is not None for c in (c0, b1.conv1, b1.conv2, b2.conv1, b2.conv2, b2.downsample[0])))
-                if ok:
-                    f32 = lambda t: t.detach().float().contiguous()
-                    self._front_c = dict(
-                        stem=(f32(c0.weight).reshape(16, 147).contiguous(), f32(c0.bias),
-                              f32(b1.conv1.weight).permute(0, 2, 3, 1).reshape(16, 144).contiguous(), f32(b1.conv1.bias)),
-                        l1c2=Engine.small_planes(b1.conv2.weight) + (f32(b1.conv2.bias),),
-                        l2c1=Engine.small_planes(b2.conv1.weight, b2.downsample[0].weight)
-                        + (torch.cat([f32(b2.conv1.bias), f32(b2.downsample[0].bias)]).contiguous(),),
-                        l2c2=Engine.small_planes(b2.conv2.weight) + (f32(b2.conv2.bias),))
-            self._stem_c16 = None
-            if self.arch == 'C' and self.folded and dtype == torch.bfloat16:
-                # bf16 DRN-C: conv1 + layer1's first convolution as the fused bf16 stem (which also stores conv1's output, the
-                # block's residual); the rest of layers 1 / 2 runs on spa_conv_bf16_light through the modules
-                c0, b1 = self.conv1, self.layer1[0]
-                if (len(self.layer1) == 1 and b1.residual and b1.downsample is None and c0.bias is not None
-                        and b1.conv1.bias is not None and b1.conv1.stride == (1, 1) and b1.conv1.dilation == (1, 1)):
-                    self._stem_c16 = (c0.weight.detach().float().reshape(16, 147).contiguous(), c0.bias.detach().float().contiguous(),
-                                      b1.conv1.weight.detach().float().permute(0, 2, 3, 1).reshape(16, 144).contiguous(),
-                                      b1.conv1.bias.detach().float().contiguous())
-            if self.arch == 'D' and self.folded and dtype in (torch.float32, torch.bfloat16):
-                # operands of libspalign's fused stem kernel (normalise + layer0 + layer1)
-                c0, c1 = self.layer0[0], self.layer1[0]
-                self._stem = (c0.weight.detach().float().reshape(16, 147).contiguous(),
-                              c0.bias.detach().float().contiguous(),
-                              c1.weight.detach().float().permute(0, 2, 3, 1).reshape(16, 144).contiguous(),
-                              c1.bias.detach().float().contiguous())
+                self._front_c = dict(
+                    stem=_pack_stem(c0, b1.conv1),
+                    l1c2=Engine.small_planes(b1.conv2.weight) + (f32(b1.conv2.bias),),
+                    l2c1=Engine.small_planes(b2.conv1.weight, b2.downsample[0].weight)
+                    + (torch.cat([f32(b2.conv1.bias), f32(b2.downsample[0].bias)]).contiguous(),),
+                    l2c2=Engine.small_planes(b2.conv2.weight) + (f32(b2.conv2.bias),))
+            # bf16 DRN-C: conv1 + layer1's first convolution as the fused bf16 stem (which also stores conv1's output, the
+            # block's residual); the rest of layers 1 / 2 runs on spa_conv_bf16_light through the modules
+            self._stem_c16 = _pack_stem(self.conv1, self.layer1[0].conv1) if '_stem_c16' in fam else None
+            # libspalign's fused stem kernel of arch D (normalise + layer0 + layer1)
+            self._stem = _pack_stem(self.layer0[0], self.layer1[0]) if '_stem' in fam else None
         return self
 
     # -- forward ---------------------------------------------------------------------------------
@@ -589,44 +710,31 @@ class DRN(nn.Module):
         x = (x.double() / std).float()
         return x
 
+    def front_families(self, dtype):
+        """Which front operands prepare() packs for a network of `dtype`: '_front_c', '_stem_c16', '_stem' (the attributes)."""
+        if not self.folded:
+            return ()
+        if self.arch == 'D':
+            return ('_stem',) if dtype in (F32, BF16) else ()
+        c0, b1, b2 = self.conv1, self.layer1[0], self.layer2[0]
+        if dtype == F32 and (len(self.layer1) == 1 and len(self.layer2) == 1 and b1.residual and b1.downsample is None and b2.residual
+                             and b2.downsample is not None and b2.conv1.stride == (2, 2) and b2.downsample[0].stride == (2, 2)
+                             and all(c.bias is not None for c in (c0, b1.conv1, b1.conv2, b2.conv1, b2.conv2, b2.downsample[0]))):
+            return ('_front_c',)
+        if dtype == BF16 and (len(self.layer1) == 1 and b1.residual and b1.downsample is None and c0.bias is not None
+                              and b1.conv1.bias is not None and b1.conv1.stride == (1, 1) and b1.conv1.dilation == (1, 1)):
+            return ('_stem_c16',)
+        return ()
+
     def _forward_chunk(self, xc):
         """One sub-batch: raw (b,3,H,W) float32 0..255 -> the 8 maps."""
         eng = _EPILOGUE['engine']
-        fc = getattr(self, '_front_c', None)
-        if (eng is not None and xc.is_cuda and fc is not None and self.use_fused_stem and _EPILOGUE['split_gemm']
-                and _EPILOGUE['own_conv32'] and self.compute_dtype == torch.float32):
-            # DRN-C: conv1 .. layer2 on libspalign's kernels (no MIOpen convolution, no separate epilogue pass)
-            E = _EPILOGUE
-            B, _, H, W = xc.shape
-            a1, y0 = eng.drn_stem_d(xc.float().contiguous(), *fc['stem'], dtype=torch.float32, split=True, want_layer0=True)
-            l1, _ = eng.conv_small_f16s(a1, fc['l1c2'][0], fc['l1c2'][1], fc['l1c2'][2], 16, 1, 0, y0, True, amax_in=a1._spa_amax)
-            a2, proj = eng.conv_small_f16s(l1, fc['l2c1'][0], fc['l2c1'][1], fc['l2c1'][2], 32, 2, 32, None, True, amax_in=l1._spa_amax)
-            l2, _ = eng.conv_small_f16s(a2, fc['l2c2'][0], fc['l2c2'][1], fc['l2c2'][2], 32, 1, 0, proj, True, amax_in=a2._spa_amax)
-            Ho, Wo = a2.shape[2], a2.shape[3]
-            fl2 = 2.0 * B * (H * W * 16 * 9 * 16 + Ho * Wo * (32 * 9 * 16 + 32 * 16 + 32 * 9 * 32))
-            by2 = 4.0 * B * (H * W * (16 + 16 + 16) + H * W * 16 + Ho * Wo * (32 + 32) + Ho * Wo * (32 + 32 + 32))
-            E['conv16_flops'] += fl2
-            E['conv16_bytes'] += by2
-            E['conv16_launches'] += 3
-            _c16('front', fl2, by2, 3)
-            return self.forward_maps(None, front_maps=[l1, l2])
-        sc16 = getattr(self, '_stem_c16', None)
-        if (eng is not None and xc.is_cuda and sc16 is not None and self.use_fused_stem and _EPILOGUE['own_conv']
-                and self.compute_dtype == torch.bfloat16):
-            a1, y0 = eng.drn_stem_d(xc.float().contiguous(), *sc16, dtype=torch.bfloat16, want_layer0=True)
-            b1 = self.layer1[0]
-            l1 = conv_bias_act(b1.conv2, b1.bn2, a1, y0, True)
-            return self.forward_maps(None, front_maps=[l1])
-        if eng is not None and xc.is_cuda and getattr(self, '_stem', None) is not None and self.use_fused_stem:
-            l1 = eng.drn_stem_d(xc.float().contiguous(), *self._stem, dtype=self.compute_dtype,
-                                split=_EPILOGUE['split_gemm'] and self.compute_dtype == torch.float32)
-            return self.forward_maps(None, layer1_out=l1)
-        if eng is not None and xc.is_cuda:
-            xi = eng.drn_normalise(xc.float().contiguous(), self.compute_dtype)
-        else:
-            xi = self.normalise(xc.float())
-            xi = xi.to(self.compute_dtype).contiguous(memory_format=torch.channels_last)
-        return self.forward(xi)[1]
+        fam = tuple(n for n in ('_front_c', '_stem_c16', '_stem') if getattr(self, n, None) is not None)
+        route = choose_chunk(fam, self.use_fused_stem, self.compute_dtype, eng is not None and xc.is_cuda, _flags())
+        count, launch = _CHUNK[route]
+        if count is not None:
+            count(*xc.shape)
+        return launch(self, eng, xc)
 
     @torch.no_grad()
     def batch_predict(self, x, sub_batch=None, need=None, streams=1):
@@ -689,9 +797,7 @@ class DRN(nn.Module):
         shape whose capture failed (and says so once)."""
         E = _EPILOGUE
         eng = E['engine']
-        key = (tuple(x.shape), x.dtype, tuple(x.stride()), self.compute_dtype, tuple(sorted(keep)), E['split_gemm'], E['own_conv'],
-               E['own_conv32'], E['winograd'], id(eng), self.use_fused_stem,
-               os.environ.get('SPA_WINO_MIN_CIN'), eng.debug_get(4, 2))
+        key = (tuple(x.shape), x.dtype, tuple(x.stride()), self.compute_dtype, tuple(sorted(keep))) + _flags() + (id(eng), self.use_fused_stem)
         cache = self.__dict__.setdefault('_graphs', {})
         # a captured launch holds the addresses of libspalign's workspaces (packed stem weights, the zero line, ...): when one of
         # them has been re-allocated since (another model or a larger shape on the same context), every graph is stale
