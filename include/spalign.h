@@ -621,8 +621,20 @@ int spa_segnet_train_input(spa_ctx *ctx, const uint8_t *src, int32_t B, int32_t 
 int spa_segnet_train_label(spa_ctx *ctx, const void *src, int32_t is_float, int32_t B, int32_t C, int32_t H, int32_t W,
                            int32_t h, int32_t w, const int32_t *yi, const int32_t *xi, const uint8_t *flip, void *out,
                            void *stream);
+/* The two above with the source given as a device table of B addresses instead of one contiguous batch
+ * (train_segnet.py --device_cache_gb: a batch assembled from cached frames and an uploaded slab): srcs[b] is the
+ * decoded frame (H,W,3) uint8, or the label array (C,H,W) uint8 / float32, of example b.  The addresses need no
+ * alignment (float32 labels are read byte-wise) and the same address may appear more than once.  Same passes, tables,
+ * stores and bits; same refusals, and a NULL table; a refused call launches nothing. */
+int spa_segnet_train_input_ptrs(spa_ctx *ctx, const uint8_t *const *srcs, int32_t B, int32_t H, int32_t W, int32_t h,
+                                int32_t w, int32_t backend, const int32_t *xb, const void *xk, int32_t ksx,
+                                const int32_t *yb, const void *yk, int32_t ksy, const double *shift,
+                                const uint8_t *flip, float *tmp, float *out, void *stream);
+int spa_segnet_train_label_ptrs(spa_ctx *ctx, const void *const *srcs, int32_t is_float, int32_t B, int32_t C,
+                                int32_t H, int32_t W, int32_t h, int32_t w, const int32_t *yi, const int32_t *xi,
+                                const uint8_t *flip, void *out, void *stream);
 
-/* ---- SegNet-Basic training (train_segnet.py --model basic) ----------------------------------------------------
+/* ---- SegNet-Basic training (train_segnet.py --model basic)----------------------------------------------------
  * The 7x7 convolutions (padding 3, stride 1, no bias) of the training step on the float32 matrix cores; BatchNorm,
  * ReLU, pooling and the loss are the caller's.  (H, W) is the convolution's resolution: multiples of 16 for conv1
  * (the network input), even for the 64-channel layers (1/2 .. 1/8 of it).  wt is the

@@ -160,6 +160,10 @@ PROTOTYPES = {
                                               c_p, c_i32, c_p, c_p, c_p, c_p, c_p]),
     'spa_segnet_train_label': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p,
                                               c_p, c_p]),
+    'spa_segnet_train_input_ptrs': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_i32,
+                                                   c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p]),
+    'spa_segnet_train_label_ptrs': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p,
+                                                   c_p, c_p, c_p]),
     'spa_segnet_train_forward': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p,
                                                 c_p, c_p]),
     'spa_segnet_train_dgrad': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),

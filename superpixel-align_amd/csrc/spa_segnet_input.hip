@@ -21,14 +21,22 @@
 // One thread owns one output pixel of one pass (its three channels); no atomics, no host synchronisation.
 #include "spa_common.h"
 
-// the sample (b, c, y, x) of the pass's source: the decoded bytes, or the float32 planes of the pass before
-template <bool U8> struct InSrc;
-template <> struct InSrc<true> {
+// the sample (b, c, y, x) of the pass's source: the float32 planes of the pass before (IN_F32), the decoded bytes of
+// one contiguous batch (IN_U8), or the decoded bytes of B frames wherever they lie (IN_U8_PTRS: a device table of B
+// addresses, the _ptrs entry points).  The accessor is all that differs between the entry points.
+enum { IN_F32 = 0, IN_U8 = 1, IN_U8_PTRS = 2 };
+template <int KIND> struct InSrc;
+template <> struct InSrc<IN_U8> {
     const uint8_t *p; int H, W;
     __device__ __forceinline__ float at(int b, int c, int y, int x) const
     { return (float)p[(((long long)b * H + y) * W + x) * 3 + c]; }
 };
-template <> struct InSrc<false> {
+template <> struct InSrc<IN_U8_PTRS> {
+    const uint8_t *const *p; int H, W;
+    __device__ __forceinline__ float at(int b, int c, int y, int x) const
+    { return (float)p[b][((long long)y * W + x) * 3 + c]; }
+};
+template <> struct InSrc<IN_F32> {
     const float *p; int H, W;
     __device__ __forceinline__ float at(int b, int c, int y, int x) const
     { return p[(((long long)b * 3 + c) * H + y) * W + x]; }
@@ -46,8 +54,8 @@ __device__ __forceinline__ void in_store(float v, int b, int c, int y, int x, in
 // One pass along X (AXIS 0) or Y (AXIS 1): src (.., H, W) -> (.., oh, ow) with oh == H (AXIS 0) or ow == W (AXIS 1).
 // CV false: bounds (n_out, 2), taps (n_out, ksize) double.  CV true: bounds (n_out, 4) clamped indices, taps (n_out, 4)
 // float.  LAST: the store applies shift and flip; otherwise plain planar float32.
-template <int AXIS, bool U8, bool CV, bool LAST>
-__global__ __launch_bounds__(256) void k_in_pass(InSrc<U8> src, int oh, int ow, const int32_t *__restrict__ bounds,
+template <int AXIS, int KIND, bool CV, bool LAST>
+__global__ __launch_bounds__(256) void k_in_pass(InSrc<KIND> src, int oh, int ow, const int32_t *__restrict__ bounds,
                                                  const void *__restrict__ taps, int ksize,
                                                  const double *__restrict__ shift, const uint8_t *__restrict__ flip,
                                                  float *__restrict__ out)
@@ -90,7 +98,8 @@ __global__ __launch_bounds__(256) void k_in_pass(InSrc<U8> src, int oh, int ow, 
 }
 
 // equal sizes: the image is widened only (then shifted and flipped)
-__global__ __launch_bounds__(256) void k_in_widen(InSrc<true> src, const double *__restrict__ shift,
+template <int KIND>
+__global__ __launch_bounds__(256) void k_in_widen(InSrc<KIND> src, const double *__restrict__ shift,
                                                   const uint8_t *__restrict__ flip, float *__restrict__ out)
 {
     const int b = blockIdx.z, y = blockIdx.y;
@@ -100,26 +109,27 @@ __global__ __launch_bounds__(256) void k_in_widen(InSrc<true> src, const double 
     for (int c = 0; c < 3; ++c) in_store(src.at(b, c, y, x), b, c, y, x, src.H, src.W, shift, flip, out);
 }
 
-template <int AXIS, bool U8, bool CV, bool LAST>
-static void in_launch(hipStream_t s, InSrc<U8> src, int B, int oh, int ow, const int32_t *bounds, const void *taps,
+template <int AXIS, int KIND, bool CV, bool LAST>
+static void in_launch(hipStream_t s, InSrc<KIND> src, int B, int oh, int ow, const int32_t *bounds, const void *taps,
                       int ksize, const double *shift, const uint8_t *flip, float *out)
 {
-    hipLaunchKernelGGL((k_in_pass<AXIS, U8, CV, LAST>), dim3((ow + 255) / 256, oh, B), dim3(256), 0, s, src, oh, ow,
+    hipLaunchKernelGGL((k_in_pass<AXIS, KIND, CV, LAST>), dim3((ow + 255) / 256, oh, B), dim3(256), 0, s, src, oh, ow,
                        bounds, taps, ksize, shift, flip, out);
 }
 
-extern "C" int spa_segnet_train_input(spa_ctx *ctx, const uint8_t *src, int32_t B, int32_t H, int32_t W, int32_t h,
-                                      int32_t w, int32_t backend, const int32_t *xb, const void *xk, int32_t ksx,
-                                      const int32_t *yb, const void *yk, int32_t ksy, const double *shift,
-                                      const uint8_t *flip, float *tmp, float *out, void *stream)
+// the passes of both image entry points; KIND: how the decoded bytes are found (IN_U8 or IN_U8_PTRS)
+template <int KIND>
+static int in_image(spa_ctx *ctx, InSrc<KIND> in, int32_t B, int32_t h, int32_t w, int32_t backend, const int32_t *xb,
+                    const void *xk, int32_t ksx, const int32_t *yb, const void *yk, int32_t ksy, const double *shift,
+                    const uint8_t *flip, float *tmp, float *out, void *stream)
 {
-    SPA_ARG(ctx && src && out && B > 0 && H > 0 && W > 0 && h > 0 && w > 0);
+    const int H = in.H, W = in.W;
+    SPA_ARG(ctx && in.p && out && B > 0 && H > 0 && W > 0 && h > 0 && w > 0);
     SPA_ARG(B < 65536 && H < 65536 && h < 65536);
     SPA_ARG(backend == 0 || backend == 1);
     hipStream_t s = spa_stream(stream);
-    const InSrc<true> in{src, H, W};
     if (H == h && W == w) {
-        hipLaunchKernelGGL(k_in_widen, dim3((W + 255) / 256, H, B), dim3(256), 0, s, in, shift, flip, out);
+        hipLaunchKernelGGL(k_in_widen<KIND>, dim3((W + 255) / 256, H, B), dim3(256), 0, s, in, shift, flip, out);
         SPA_LAUNCH_CHECK();
         return SPA_OK;
     }
@@ -129,51 +139,105 @@ extern "C" int spa_segnet_train_input(spa_ctx *ctx, const uint8_t *src, int32_t 
     SPA_ARG(!do_y || (yb && yk && (cv || ksy > 0)));
     SPA_ARG(!(do_x && do_y) || tmp);
     if (do_x && do_y) {
-        const InSrc<false> mid{tmp, H, w};
+        const InSrc<IN_F32> mid{tmp, H, w};
         if (cv) {
-            in_launch<0, true, true, false>(s, in, B, H, w, xb, xk, 4, nullptr, nullptr, tmp);
-            in_launch<1, false, true, true>(s, mid, B, h, w, yb, yk, 4, shift, flip, out);
+            in_launch<0, KIND, true, false>(s, in, B, H, w, xb, xk, 4, nullptr, nullptr, tmp);
+            in_launch<1, IN_F32, true, true>(s, mid, B, h, w, yb, yk, 4, shift, flip, out);
         } else {
-            in_launch<0, true, false, false>(s, in, B, H, w, xb, xk, ksx, nullptr, nullptr, tmp);
-            in_launch<1, false, false, true>(s, mid, B, h, w, yb, yk, ksy, shift, flip, out);
+            in_launch<0, KIND, false, false>(s, in, B, H, w, xb, xk, ksx, nullptr, nullptr, tmp);
+            in_launch<1, IN_F32, false, true>(s, mid, B, h, w, yb, yk, ksy, shift, flip, out);
         }
     } else if (do_x) {
-        in_launch<0, true, false, true>(s, in, B, h, w, xb, xk, ksx, shift, flip, out);
+        in_launch<0, KIND, false, true>(s, in, B, h, w, xb, xk, ksx, shift, flip, out);
     } else {
-        in_launch<1, true, false, true>(s, in, B, h, w, yb, yk, ksy, shift, flip, out);
+        in_launch<1, KIND, false, true>(s, in, B, h, w, yb, yk, ksy, shift, flip, out);
     }
     SPA_LAUNCH_CHECK();
     return SPA_OK;
 }
 
+extern "C" int spa_segnet_train_input(spa_ctx *ctx, const uint8_t *src, int32_t B, int32_t H, int32_t W, int32_t h,
+                                      int32_t w, int32_t backend, const int32_t *xb, const void *xk, int32_t ksx,
+                                      const int32_t *yb, const void *yk, int32_t ksy, const double *shift,
+                                      const uint8_t *flip, float *tmp, float *out, void *stream)
+{
+    return in_image(ctx, InSrc<IN_U8>{src, H, W}, B, h, w, backend, xb, xk, ksx, yb, yk, ksy, shift, flip, tmp, out,
+                    stream);
+}
+
+extern "C" int spa_segnet_train_input_ptrs(spa_ctx *ctx, const uint8_t *const *srcs, int32_t B, int32_t H, int32_t W,
+                                           int32_t h, int32_t w, int32_t backend, const int32_t *xb, const void *xk,
+                                           int32_t ksx, const int32_t *yb, const void *yk, int32_t ksy,
+                                           const double *shift, const uint8_t *flip, float *tmp, float *out,
+                                           void *stream)
+{
+    return in_image(ctx, InSrc<IN_U8_PTRS>{srcs, H, W}, B, h, w, backend, xb, xk, ksx, yb, yk, ksy, shift, flip, tmp,
+                    out, stream);
+}
+
 // labels: out[b, c, y, x'] = (To)src[b, c, yi[y], xi[x]], x' = x or w - 1 - x.  Planes = B * C.
-template <typename Ti, typename To>
-__global__ __launch_bounds__(256) void k_in_label(const Ti *__restrict__ src, int C, int H, int W, int h, int w,
+// The plane p of the source: in one contiguous batch, or in the example p / C of a device table of B addresses (the
+// _ptrs entry point), which need not be aligned for Ti: the value is read byte-wise there.
+template <typename Ti, bool PTRS> struct LabSrc;
+template <typename Ti> struct LabSrc<Ti, false> {
+    const Ti *p;
+    __device__ __forceinline__ Ti at(int plane, int C, long long plane_size, long long i) const
+    { return p[plane * plane_size + i]; }
+};
+template <typename Ti> struct LabSrc<Ti, true> {
+    const uint8_t *const *p;
+    __device__ __forceinline__ Ti at(int plane, int C, long long plane_size, long long i) const
+    {
+        Ti v;
+        __builtin_memcpy(&v, p[plane / C] + ((plane % C) * plane_size + i) * (long long)sizeof(Ti), sizeof(Ti));
+        return v;
+    }
+};
+
+template <typename Ti, typename To, bool PTRS>
+__global__ __launch_bounds__(256) void k_in_label(LabSrc<Ti, PTRS> src, int C, int H, int W, int h, int w,
                                                   const int32_t *__restrict__ yi, const int32_t *__restrict__ xi,
                                                   const uint8_t *__restrict__ flip, To *__restrict__ out)
 {
     const int p = blockIdx.z, y = blockIdx.y;
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x >= w) return;
-    const Ti v = src[((long long)p * H + yi[y]) * W + xi[x]];
+    const Ti v = src.at(p, C, (long long)H * W, (long long)yi[y] * W + xi[x]);
     const int xo = (flip && flip[p / C]) ? w - 1 - x : x;
     out[((long long)p * h + y) * w + xo] = (To)v;
+}
+
+template <bool PTRS>
+static int in_label(spa_ctx *ctx, const void *src, int32_t is_float, int32_t B, int32_t C, int32_t H, int32_t W,
+                    int32_t h, int32_t w, const int32_t *yi, const int32_t *xi, const uint8_t *flip, void *out,
+                    void *stream)
+{
+    SPA_ARG(ctx && src && out && yi && xi && B > 0 && C > 0 && H > 0 && W > 0 && h > 0 && w > 0);
+    SPA_ARG((long long)B * C < 65536 && h < 65536);
+    hipStream_t s = spa_stream(stream);
+    const dim3 grid((w + 255) / 256, h, B * C);
+    typedef decltype(LabSrc<float, PTRS>::p) Pf;
+    typedef decltype(LabSrc<uint8_t, PTRS>::p) Pb;
+    if (is_float)
+        hipLaunchKernelGGL((k_in_label<float, float, PTRS>), grid, dim3(256), 0, s, LabSrc<float, PTRS>{(Pf)src}, C, H,
+                           W, h, w, yi, xi, flip, (float *)out);
+    else
+        hipLaunchKernelGGL((k_in_label<uint8_t, int32_t, PTRS>), grid, dim3(256), 0, s, LabSrc<uint8_t, PTRS>{(Pb)src},
+                           C, H, W, h, w, yi, xi, flip, (int32_t *)out);
+    SPA_LAUNCH_CHECK();
+    return SPA_OK;
 }
 
 extern "C" int spa_segnet_train_label(spa_ctx *ctx, const void *src, int32_t is_float, int32_t B, int32_t C, int32_t H,
                                       int32_t W, int32_t h, int32_t w, const int32_t *yi, const int32_t *xi,
                                       const uint8_t *flip, void *out, void *stream)
 {
-    SPA_ARG(ctx && src && out && yi && xi && B > 0 && C > 0 && H > 0 && W > 0 && h > 0 && w > 0);
-    SPA_ARG((long long)B * C < 65536 && h < 65536);
-    hipStream_t s = spa_stream(stream);
-    const dim3 grid((w + 255) / 256, h, B * C);
-    if (is_float)
-        hipLaunchKernelGGL((k_in_label<float, float>), grid, dim3(256), 0, s, (const float *)src, C, H, W, h, w, yi, xi,
-                           flip, (float *)out);
-    else
-        hipLaunchKernelGGL((k_in_label<uint8_t, int32_t>), grid, dim3(256), 0, s, (const uint8_t *)src, C, H, W, h, w, yi,
-                           xi, flip, (int32_t *)out);
-    SPA_LAUNCH_CHECK();
-    return SPA_OK;
+    return in_label<false>(ctx, src, is_float, B, C, H, W, h, w, yi, xi, flip, out, stream);
+}
+
+extern "C" int spa_segnet_train_label_ptrs(spa_ctx *ctx, const void *const *srcs, int32_t is_float, int32_t B,
+                                           int32_t C, int32_t H, int32_t W, int32_t h, int32_t w, const int32_t *yi,
+                                           const int32_t *xi, const uint8_t *flip, void *out, void *stream)
+{
+    return in_label<true>(ctx, (const void *)srcs, is_float, B, C, H, W, h, w, yi, xi, flip, out, stream);
 }

@@ -999,16 +999,19 @@ class Engine(object):
             raise SpalignError('flip must be (B,) uint8, got %s' % (tuple(flip.shape),))
         return flip
 
-    def segnet_train_input(self, src, shape, shift=None, flip=None, backend=None):
-        """Decoded frames (B,H,W,3) uint8 -> the training images (B,3,h,w) float32 0..255 with the bits of
-        ZippedEstimatedCityscapesDataset.get_example: each channel resized as a float image (Pillow's mode 'F' BICUBIC,
-        or with backend 'cv2' resize_bicubic_float's OpenCV form; backend None: cli.RESIZE_BACKEND), then shift (B,3)
-        float64 (pca_lighting_shift of each image's draw) added as numpy's float32 += float64, then the images with
-        flip (B,) uint8 != 0 mirrored.  Equal sizes: widened only."""
-        src = _req(src, torch.uint8, 'src')
-        if src.dim() != 4 or src.shape[3] != 3:
-            raise SpalignError('segnet_train_input: src must be (B,H,W,3) uint8, got %s' % (tuple(src.shape),))
-        B, H, W, _ = src.shape
+    @staticmethod
+    def _input_out(out, shape, dtype, device):
+        """the output of an input-stage wrapper: a new tensor, or the caller's (tests hand in poisoned buffers)"""
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=device)
+        _req(out, dtype, 'out')
+        if tuple(out.shape) != tuple(shape):
+            raise SpalignError('out must be %s, got %s' % (tuple(shape), tuple(out.shape)))
+        return out
+
+    def _segnet_train_input(self, fn, src, B, H, W, shape, shift, flip, backend, out):
+        """segnet_train_input and segnet_train_input_ptrs below: src is the batch or the table of its addresses"""
+        B, H, W = int(B), int(H), int(W)
         h, w = int(shape[0]), int(shape[1])
         backend = self._input_backend(backend)
         if shift is not None:
@@ -1016,44 +1019,95 @@ class Engine(object):
             if tuple(shift.shape) != (B, 3):
                 raise SpalignError('shift must be (B,3) float64, got %s' % (tuple(shift.shape),))
         flip = self._flip(flip, B)
-        out = torch.empty((B, 3, h, w), dtype=torch.float32, device=src.device)
+        out = self._input_out(out, (B, 3, h, w), torch.float32, self.device if src is None else src.device)
         xb = xk = yb = yk = tmp = None
         ksx = ksy = 0
-        if (H, W) != (h, w):
+        if (H, W) != (h, w) and B > 0:
             cv = backend == 'cv2'
             if cv or W != w:
                 xb, xk, ksx = self._input_tables('cubic', W, w, backend)
             if cv or H != h:
                 yb, yk, ksy = self._input_tables('cubic', H, h, backend)
             if xb is not None and yb is not None:
-                tmp = torch.empty((B, 3, H, w), dtype=torch.float32, device=src.device)
-        check(self._lib.spa_segnet_train_input(self._ctx, _ptr(src), B, H, W, h, w, 1 if backend == 'cv2' else 0,
-                                               _ptr(xb), _ptr(xk), ksx, _ptr(yb), _ptr(yk), ksy, _ptr(shift),
-                                               _ptr(flip), _ptr(tmp), _ptr(out), self._s()))
+                tmp = torch.empty((B, 3, H, w), dtype=torch.float32, device=out.device)
+        check(fn(self._ctx, _ptr(src), B, H, W, h, w, 1 if backend == 'cv2' else 0, _ptr(xb), _ptr(xk), ksx, _ptr(yb),
+                 _ptr(yk), ksy, _ptr(shift), _ptr(flip), _ptr(tmp), _ptr(out), self._s()))
         return out
 
-    def segnet_train_label(self, src, shape, flip=None, backend=None):
-        """The labels of the same examples: uint8 masks (B,H,W) -> int32 (B,h,w), or float32 scores (B,C,H,W) ->
-        float32 (B,C,h,w), resized as resize_nearest_label does (Pillow's NEAREST, or cli.resize_nearest with backend
-        'cv2') and mirrored where flip (B,) uint8 != 0."""
-        if src.dtype == torch.uint8 and src.dim() == 3:
-            src = _req(src, torch.uint8, 'src')
-            is_float, C, out_dtype = 0, 1, torch.int32
-        elif src.dtype == torch.float32 and src.dim() == 4:
-            src = _req(src, torch.float32, 'src')
-            is_float, C, out_dtype = 1, int(src.shape[1]), torch.float32
-        else:
-            raise SpalignError('segnet_train_label: src must be (B,H,W) uint8 or (B,C,H,W) float32')
-        B, (H, W) = src.shape[0], src.shape[-2:]
+    def segnet_train_input(self, src, shape, shift=None, flip=None, backend=None, out=None):
+        """Decoded frames (B,H,W,3) uint8 -> the training images (B,3,h,w) float32 0..255 with the bits of
+        ZippedEstimatedCityscapesDataset.get_example: each channel resized as a float image (Pillow's mode 'F' BICUBIC,
+        or with backend 'cv2' resize_bicubic_float's OpenCV form; backend None: cli.RESIZE_BACKEND), then shift (B,3)
+        float64 (pca_lighting_shift of each image's draw) added as numpy's float32 += float64, then the images with
+        flip (B,) uint8 != 0 mirrored.  Equal sizes: widened only.  out: the caller's (B,3,h,w) float32 tensor."""
+        src = _req(src, torch.uint8, 'src')
+        if src.dim() != 4 or src.shape[3] != 3:
+            raise SpalignError('segnet_train_input: src must be (B,H,W,3) uint8, got %s' % (tuple(src.shape),))
+        B, H, W, _ = src.shape
+        return self._segnet_train_input(self._lib.spa_segnet_train_input, src, B, H, W, shape, shift, flip, backend,
+                                        out)
+
+    @staticmethod
+    def _address_table(table, B):
+        """a _ptrs wrapper's table: (B,) int64 device addresses; None is handed on as NULL (the library refuses it)"""
+        if table is not None:
+            _req(table, torch.int64, 'table')
+            if tuple(table.shape) != (int(B),):
+                raise SpalignError('table must be (B,) int64 device addresses, got %s' % (tuple(table.shape),))
+        return table
+
+    def segnet_train_input_ptrs(self, table, B, src_shape, shape, shift=None, flip=None, backend=None, out=None):
+        """segnet_train_input over frames that lie anywhere in device memory: table (B,) int64 on the device, the
+        address of every example's decoded frame (H,W,3) uint8, src_shape = (H, W).  The addresses need no alignment
+        and may repeat; whoever builds the table keeps the frames alive until the launch has run.  Same bits."""
+        table = self._address_table(table, B)
+        return self._segnet_train_input(self._lib.spa_segnet_train_input_ptrs, table, B, src_shape[0], src_shape[1],
+                                        shape, shift, flip, backend, out)
+
+    def _segnet_train_label(self, fn, src, is_float, B, C, H, W, lead, shape, flip, backend, out):
+        B, C, H, W = int(B), int(C), int(H), int(W)
         h, w = int(shape[0]), int(shape[1])
         backend = self._input_backend(backend)
         flip = self._flip(flip, B)
         yi = self._input_tables('nearest', H, h, backend)
         xi = self._input_tables('nearest', W, w, backend)
-        out = torch.empty(tuple(src.shape[:-2]) + (h, w), dtype=out_dtype, device=src.device)
-        check(self._lib.spa_segnet_train_label(self._ctx, _ptr(src), is_float, B, C, H, W, h, w, _ptr(yi), _ptr(xi),
-                                               _ptr(flip), _ptr(out), self._s()))
+        out = self._input_out(out, tuple(lead) + (h, w), torch.float32 if is_float else torch.int32,
+                              self.device if src is None else src.device)
+        check(fn(self._ctx, _ptr(src), is_float, B, C, H, W, h, w, _ptr(yi), _ptr(xi), _ptr(flip), _ptr(out),
+                 self._s()))
         return out
+
+    def segnet_train_label(self, src, shape, flip=None, backend=None, out=None):
+        """The labels of the same examples: uint8 masks (B,H,W) -> int32 (B,h,w), or float32 scores (B,C,H,W) ->
+        float32 (B,C,h,w), resized as resize_nearest_label does (Pillow's NEAREST, or cli.resize_nearest with backend
+        'cv2') and mirrored where flip (B,) uint8 != 0.  out: the caller's tensor of that shape and dtype."""
+        if src.dtype == torch.uint8 and src.dim() == 3:
+            src = _req(src, torch.uint8, 'src')
+            is_float, C = 0, 1
+        elif src.dtype == torch.float32 and src.dim() == 4:
+            src = _req(src, torch.float32, 'src')
+            is_float, C = 1, int(src.shape[1])
+        else:
+            raise SpalignError('segnet_train_label: src must be (B,H,W) uint8 or (B,C,H,W) float32')
+        B, (H, W) = src.shape[0], src.shape[-2:]
+        return self._segnet_train_label(self._lib.spa_segnet_train_label, src, is_float, B, C, H, W, src.shape[:-2],
+                                        shape, flip, backend, out)
+
+    def segnet_train_label_ptrs(self, table, B, src_shape, dtype, shape, flip=None, backend=None, out=None):
+        """segnet_train_label over label arrays that lie anywhere in device memory: table (B,) int64 on the device,
+        the address of every example's array; src_shape (H,W) with dtype uint8 (masks -> int32 (B,h,w)) or (C,H,W)
+        with dtype float32 (scores -> float32 (B,C,h,w)).  The addresses need no alignment and may repeat."""
+        src_shape = tuple(int(v) for v in src_shape)
+        dtype = np.dtype(dtype)
+        if dtype == np.uint8 and len(src_shape) == 2:
+            is_float, C, lead = 0, 1, (int(B),)
+        elif dtype == np.float32 and len(src_shape) == 3:
+            is_float, C, lead = 1, src_shape[0], (int(B), src_shape[0])
+        else:
+            raise SpalignError('segnet_train_label_ptrs: the arrays must be (H,W) uint8 or (C,H,W) float32')
+        table = self._address_table(table, B)
+        return self._segnet_train_label(self._lib.spa_segnet_train_label_ptrs, table, is_float, B, C, src_shape[-2],
+                                        src_shape[-1], lead, shape, flip, backend, out)
 
     # ---- SegNet-Basic training (segnet_train.py).  Maps are (B,H,W,64) contiguous tensors (channels-last storage);
     # conv1's input is the planar (B,3,H,W) float32 image 0..255.

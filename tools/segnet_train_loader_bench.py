@@ -21,6 +21,15 @@ B / (N / decode_s)) and loader_ms / bound_ms.  Synthetic frames carry noise and 
 their PNGs decode slower than Cityscapes frames do; (a), (b) and (d) share that.
 
   python tools/segnet_train_loader_bench.py [--procs 4 8 16] [--steps 12] [--n_images 24] [--out FILE.json]
+
+With --device_cache_gb G the tool measures train_segnet.py --device_cache_gb instead (cache_main), in one session, per
+dtype with --fused_bn: row (c); per N of --cache_procs the uncached row (b) and the cached loader's step time and
+next() wait in epoch 1 and in epochs 2-3 (an epoch is n_images / batch iterations), with the bytes cached; the uncached
+row (b) at N = 16; one train_segnet.evaluate pass over --n_val frames with the uncached label loader, then the first and
+the second pass of the cached one; and the _ptrs input kernels against the contiguous ones on one batch, alternating
+over 5 rounds (median and spread of the per-call device time).
+
+  python tools/segnet_train_loader_bench.py --device_cache_gb 2 --out profiles/segnet_train_cache_b4.json
 """
 import argparse
 import importlib
@@ -84,9 +93,9 @@ def plain_loop(ds, it, trainer, dev, warmup, steps):
             'step_ms': times['step'] * 1e3 / steps}
 
 
-def loader_loop(ds, it, trainer, n_procs, warmup, steps):
+def loader_loop(ds, it, trainer, n_procs, warmup, steps, cache=None):
     t_start = time.perf_counter()
-    loader = sl.TrainLoader(ds, np.arange(len(ds)), it, n_procs, sl.DeviceStage(ds, trainer.eng))
+    loader = sl.TrainLoader(ds, np.arange(len(ds)), it, n_procs, sl.DeviceStage(ds, trainer.eng), cache=cache)
     started = time.perf_counter() - t_start
     try:
         waits = steps_t = 0.0
@@ -180,6 +189,154 @@ def slab_upload_row(eng, nbytes, iters):
         shm.unlink()
 
 
+def cached_epochs(ds, trainer, n_procs, cache, B, epochs=3):
+    """the cached loader from its first batch on: per epoch the wall time per iteration, the next() wait and the step"""
+    per = len(ds) // B
+    loader = sl.TrainLoader(ds, np.arange(len(ds)), st.ShuffledIterator(len(ds), B), n_procs,
+                            sl.DeviceStage(ds, trainer.eng), cache=cache)
+    rows = []
+    try:
+        for _ in range(epochs):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            waits = 0.0
+            for _ in range(per):
+                ta = time.perf_counter()
+                img, lab, _ = loader.next()
+                waits += time.perf_counter() - ta
+                trainer.step(img, lab)
+            torch.cuda.synchronize()
+            total = time.perf_counter() - t0
+            rows.append({'ms': total * 1e3 / per, 'next_ms': waits * 1e3 / per})
+    finally:
+        loader.close()
+    later = rows[1:]
+    return {'epoch1': rows[0], 'epochs2_3': {'ms': float(np.mean([r['ms'] for r in later])),
+                                             'next_ms': float(np.mean([r['next_ms'] for r in later]))},
+            'per_epoch': rows, 'iterations_per_epoch': per, 'hits': loader.cache_hits, 'misses': loader.cache_misses}
+
+
+def ptrs_rows(eng, B, src, dst, iters, rounds=5):
+    """the _ptrs input kernels against the contiguous ones on the same batch, alternating; per-call device ms"""
+    H, W = src
+    g = torch.Generator(device='cuda').manual_seed(0)
+    u8 = torch.randint(0, 256, (B, H, W, 3), generator=g, device='cuda', dtype=torch.uint8)
+    masks = torch.randint(0, 2, (B, H, W), generator=g, device='cuda', dtype=torch.uint8)
+    shift = torch.randn((B, 3), generator=g, device='cuda', dtype=torch.float64)
+    flip = torch.tensor([1, 0] * B, device='cuda', dtype=torch.uint8)[:B].contiguous()
+    tu = torch.tensor([u8[j].data_ptr() for j in range(B)], dtype=torch.int64, device='cuda')
+    tm = torch.tensor([masks[j].data_ptr() for j in range(B)], dtype=torch.int64, device='cuda')
+    fns = {'train_input': lambda: eng.segnet_train_input(u8, dst, shift, flip, 'pil'),
+           'train_input_ptrs': lambda: eng.segnet_train_input_ptrs(tu, B, src, dst, shift, flip, 'pil'),
+           'train_label_masks': lambda: eng.segnet_train_label(masks, dst, flip, 'pil'),
+           'train_label_masks_ptrs': lambda: eng.segnet_train_label_ptrs(tm, B, src, np.uint8, dst, flip, 'pil')}
+    ms = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            ms[k].append(event_ms(fn, iters))
+    return {k: {'median_ms': float(np.median(v)), 'min_ms': min(v), 'max_ms': max(v)} for k, v in ms.items()}
+
+
+def evaluate_rows(trainer, valid, eval_shape, B, n_procs, budget):
+    """one validation pass with the uncached label loader, then the first and the second pass of the cached one"""
+    fc = importlib.import_module('superpixel-align_amd.frame_cache')
+    train_segnet = importlib.import_module('train_segnet')
+    ids = list(range(len(valid)))
+
+    def timed(loader):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rep = train_segnet.evaluate(trainer, valid, eval_shape, B, ids, loader=loader)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, rep
+    out = {}
+    loader = sl.LabelLoader(valid, ids, B, n_procs, sl.DeviceLabelStage(trainer.eng))
+    try:
+        timed(loader)                                          # the predictor is built and the workers are warm
+        out['uncached_ms'], want = timed(loader)
+    finally:
+        loader.close()
+    cache = fc.DeviceFrameCache(budget, trainer.eng.device)
+    loader = sl.LabelLoader(valid, ids, B, n_procs, sl.DeviceLabelStage(trainer.eng), cache=cache)
+    try:
+        out['cached_first_ms'], r1 = timed(loader)
+        out['cached_second_ms'], r2 = timed(loader)
+    finally:
+        loader.close()
+        cache.close()
+    out.update(n_images=len(ids), procs=n_procs, bytes_cached=cache.counters()['bytes'],
+               same_report=bool(json.dumps(want, sort_keys=True) == json.dumps(r1, sort_keys=True) ==
+                                json.dumps(r2, sort_keys=True)))
+    return out
+
+
+def cache_main(a):
+    _imports()
+    import segnet_train_synth as syn
+    fc = importlib.import_module('superpixel-align_amd.frame_cache')
+    segnet = importlib.import_module('superpixel-align_amd.segnet')
+    torch.cuda.set_device(0)
+    eng = engine.Engine(0)
+    dev = eng.device
+    B, shape = a.batch, tuple(a.input_shape)
+    budget = int(a.device_cache_gb * (1 << 30))
+    root = tempfile.mkdtemp(prefix='segnet_cache_bench_')
+    try:
+        z = syn.write(root, a.n_images, a.n_val, a.frame[0], a.frame[1])
+        ds = st.ZippedEstimatedCityscapesDataset(z[0], z[1], shape, True, False)
+        valid = segnet.ZippedCityscapesRoadDataset(z[2], z[3], shape)
+        img_s, lab_s = decode_seconds(ds, 6)
+        out = {'what': 'train_segnet.py --device_cache_gb: the cached loader against --loader_procs N and the step alone',
+               'batch': B, 'frame': list(a.frame), 'input': list(shape), 'random': True, 'optimizer': 'MomentumSGD',
+               'fused_bn': True, 'n_images': a.n_images, 'budget_bytes': budget,
+               'cpus_visible': len(os.sched_getaffinity(0)), 'device': torch.cuda.get_device_name(0),
+               'decode': {'image_s': img_s, 'label_s': lab_s},
+               'kernels': ptrs_rows(eng, B, tuple(a.frame), shape, 100), 'dtypes': {}}
+        for dtype in a.dtypes:
+            np.random.seed(0)
+            trainer = st.SegNetTrainer(st.init_params(0), st.MomentumSGD(0.01, weight_decay=0.0005),
+                                       st.softmax_cross_entropy, engine=eng, dtype=dtype, fused_bn=True)
+            batch = [ds.get_example(i) for i in range(B)]
+            img = torch.from_numpy(np.stack([b[0] for b in batch])).to(dev)
+            lab = torch.from_numpy(np.stack([b[1] for b in batch])).to(dev)
+            for _ in range(2):
+                trainer.step(img, lab)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                trainer.step(img, lab)
+            torch.cuda.synchronize()
+            row = {'step_ms': (time.perf_counter() - t0) * 1e3 / a.steps, 'uncached': {}, 'cached': {}}
+            for n in sorted(set(a.cache_procs + [16])):
+                row['uncached'][str(n)] = loader_loop(ds, st.ShuffledIterator(len(ds), B), trainer, n, a.warmup,
+                                                      a.steps)
+            for n in a.cache_procs:
+                cache = fc.DeviceFrameCache(budget, dev)
+                try:
+                    r = cached_epochs(ds, trainer, n, cache, B)
+                finally:
+                    cache.close()
+                r.update(cache.counters())
+                r['cached_over_step'] = r['epochs2_3']['ms'] / row['step_ms']
+                row['cached'][str(n)] = r
+                print(dtype, 'N %d: step %.1f ms, uncached %.1f ms, cached epoch 1 %.1f ms, epochs 2-3 %.1f ms '
+                      '(next %.2f ms), %d bytes' % (n, row['step_ms'], row['uncached'][str(n)]['ms'], r['epoch1']['ms'],
+                                                    r['epochs2_3']['ms'], r['epochs2_3']['next_ms'], r['bytes']),
+                      flush=True)
+            row['uncached16_over_step'] = row['uncached']['16']['ms'] / row['step_ms']
+            row['evaluate'] = evaluate_rows(trainer, valid, tuple(a.frame), B, 4, budget)
+            out['dtypes'][dtype] = row
+            del trainer
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+    s = json.dumps(out, indent=2)
+    print(s)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as fp:
+            fp.write(s + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=4)
@@ -192,7 +349,13 @@ def main():
     ap.add_argument('--input_shape', type=int, nargs=2, default=[512, 1024])
     ap.add_argument('--dtypes', nargs='+', default=['fp32', 'bf16'], choices=['fp32', 'bf16'])
     ap.add_argument('--out', default=None)
+    ap.add_argument('--device_cache_gb', type=float, default=0.0,
+                    help='measure train_segnet.py --device_cache_gb with this budget instead (see above)')
+    ap.add_argument('--cache_procs', type=int, nargs='+', default=[1, 4])
+    ap.add_argument('--n_val', type=int, default=8)
     a = ap.parse_args()
+    if a.device_cache_gb > 0:
+        return cache_main(a)
     _imports()
     import segnet_train_synth as syn
     torch.cuda.set_device(0)

@@ -54,6 +54,13 @@ A batch whose frames are not of the first frame's size takes the host path, and 
 once) where /dev/shm cannot hold the slabs.  The same workers feed the validation passes (segnet_loader.LabelLoader): the
 validation images go through the predictor in batches of --batchsize, the confusion counts come from
 spa_segnet_label_eval and are summed on the device, and every report entry is the default run's.
+
+--device_cache_gb G (pre-parser, float, default 0; needs --loader_procs > 0, refused otherwise before anything is
+written).  With G > 0 every decoded training frame and label array, and every staged validation batch, stays in device
+memory once it has been seen (superpixel-align_amd/frame_cache.py), first come first kept up to G GB per rank, no
+eviction; an example that is kept is never decoded or uploaded again, and the input kernels read it where it lies.  The
+draws, the losses, the validation entries, the snapshots and --resume are the run's without the flag.  args.txt records
+device_cache_gb only when it is given; at close the run prints one line with the cache's counters to stderr.
 """
 import argparse
 import importlib
@@ -129,8 +136,8 @@ def get_dtype_args(argv=None):
 
 def get_pre_args(argv=None):
     """-> (namespace of this implementation's flags, the remaining arguments for get_args): --dtype (get_dtype_args),
-    --split_planes, --val_split_planes, --fused_bn, --data_parallel and --loader_procs, read by one pre-parser in front
-    of the reference flag set of get_parser."""
+    --split_planes, --val_split_planes, --fused_bn, --data_parallel, --loader_procs and --device_cache_gb, read by one
+    pre-parser in front of the reference flag set of get_parser."""
     argv = list(sys.argv[1:] if argv is None else argv)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'],
@@ -145,6 +152,9 @@ def get_pre_args(argv=None):
                      help='run as one rank of a torchrun launch (RANK / WORLD_SIZE / LOCAL_RANK)')
     pre.add_argument('--loader_procs', type=int, default=0,
                      help='decode worker processes of the input stage (per rank); 0: the loop prepares its batches itself')
+    pre.add_argument('--device_cache_gb', type=float, default=0.0,
+                     help='with --loader_procs: keep up to this many GB of decoded training and validation examples in '
+                          'device memory (per rank) and decode each of them once; 0: decode every time')
     return pre.parse_known_args(argv)
 
 
@@ -158,7 +168,8 @@ def check_split_planes(pre):
 def run_args(argv=None):
     """-> (the pre-parser's namespace, the run's arguments as args.txt records them, before a data-parallel run adds
     its world size): the reference flags plus dtype, and split_planes / val_split_planes / fused_bn / data_parallel /
-    loader_procs only where they are given."""
+    loader_procs / device_cache_gb only where they are given.  --device_cache_gb without --loader_procs is refused
+    here, before anything is written."""
     pre, argv = get_pre_args(argv)
     check_split_planes(pre)
     args = get_args(argv)
@@ -175,6 +186,13 @@ def run_args(argv=None):
         raise ValueError('--loader_procs must be >= 0, got %d' % pre.loader_procs)
     if pre.loader_procs:
         args.loader_procs = pre.loader_procs       # recorded only when given
+    if not pre.device_cache_gb >= 0:
+        raise ValueError('--device_cache_gb must be >= 0, got %r' % pre.device_cache_gb)
+    if pre.device_cache_gb > 0:
+        if not pre.loader_procs:
+            raise ValueError('--device_cache_gb keeps what the decode workers of --loader_procs deliver: give '
+                             '--loader_procs N > 0 with it')
+        args.device_cache_gb = pre.device_cache_gb # likewise
     return pre, args
 
 
@@ -274,19 +292,20 @@ def resume_check(snapshot_world_size, world_size):
                                                    else 'one process', world_size))
 
 
-def open_loader(n_procs, train, train_ids, it, stage):
+def open_loader(n_procs, train, train_ids, it, stage, cache=None):
     """-> the run's segnet_loader.TrainLoader on n_procs workers, or None where /dev/shm cannot hold its slabs: the
-    run says so once and prepares its batches itself (nothing has been drawn, so the bits are the same)."""
+    run says so once and prepares its batches itself (nothing has been drawn, so the bits are the same).  cache: the
+    run's frame_cache (--device_cache_gb); without a loader it stays unused."""
     sl = importlib.import_module('superpixel-align_amd.segnet_loader')
-    return sl.open_or_none(lambda: sl.TrainLoader(train, train_ids, it, n_procs, stage),
+    return sl.open_or_none(lambda: sl.TrainLoader(train, train_ids, it, n_procs, stage, cache=cache),
                            '--loader_procs: %s; the batches are prepared on the host')
 
 
-def open_label_loader(n_procs, valid, valid_ids, batchsize, stage, pool=None):
+def open_label_loader(n_procs, valid, valid_ids, batchsize, stage, pool=None, cache=None):
     """-> the run's segnet_loader.LabelLoader over the rank's validation indices (on the training loader's workers
     where `pool` is given), or None where /dev/shm cannot hold its slabs: one line, and validation decodes on the host"""
     sl = importlib.import_module('superpixel-align_amd.segnet_loader')
-    return sl.open_or_none(lambda: sl.LabelLoader(valid, valid_ids, batchsize, n_procs, stage, pool=pool),
+    return sl.open_or_none(lambda: sl.LabelLoader(valid, valid_ids, batchsize, n_procs, stage, pool=pool, cache=cache),
                            '--loader_procs: %s; the validation images are decoded on the host')
 
 
@@ -382,17 +401,20 @@ def main(argv=None):
     val_every = _iterations(args.val_interval, len(train_ids), args.batchsize)
     decay = args.decay_iteration if args.optimizer == 'MomentumSGD' else 0
     dev = trainer.eng.device
-    loader = val_loader = None
+    loader = val_loader = cache = None
+    if pre.device_cache_gb > 0:                    # this rank's cache of its own shards; nothing is allocated yet
+        fc = importlib.import_module('superpixel-align_amd.frame_cache')
+        cache = fc.DeviceFrameCache(int(pre.device_cache_gb * (1 << 30)), dev)
     if pre.loader_procs:                           # after --resume has set the iterator and numpy's state
         sl = importlib.import_module('superpixel-align_amd.segnet_loader')
-        loader = open_loader(pre.loader_procs, train, train_ids, it, sl.DeviceStage(train, trainer.eng))
+        loader = open_loader(pre.loader_procs, train, train_ids, it, sl.DeviceStage(train, trainer.eng), cache)
     # loader None: every batch is prepared here; else loader.next() hands out the same batches, each with the (iterator
     # state, numpy state) the plain loop has after it, which the log and the snapshots then use
     try:
         if pre.loader_procs and len(valid_ids):    # validation reads from the same workers
             val_loader = open_label_loader(pre.loader_procs, valid, valid_ids, args.batchsize,
                                            sl.DeviceLabelStage(trainer.eng),
-                                           pool=loader.workers if loader is not None else None)
+                                           pool=loader.workers if loader is not None else None, cache=cache)
         losses = []
         t0 = time.time()
         while iteration < stop:
@@ -441,6 +463,10 @@ def main(argv=None):
             val_loader.close()
         if loader is not None:
             loader.close()
+        if cache is not None:                      # after the loaders that can name its entries
+            cache.close()
+            print(('rank %d ' % rank if dp else '') + fc.summary_line(cache, loader, val_loader), file=sys.stderr,
+                  flush=True)
     if group is not None:
         group.barrier()                            # no rank leaves before rank 0's last snapshot is written
     return result_dir

@@ -36,7 +36,8 @@ independent of --split_planes and --dtype, refused with --label_dtype bf16), --f
 train_segnet.py --fused_bn: BatchNorm, ReLU, pooling and the classifier on fused kernels; passed to the training children
 only when given, with any --dtype and with --split_planes), --loader_procs (the training rounds'
 train_segnet.py --loader_procs: decode workers per rank and the input stage on the GPU, passed only when given; the
-job needs n_gpus x loader_procs CPUs for them; they also feed those rounds' validation), --label_loader_procs (the
+job needs n_gpus x loader_procs CPUs for them; they also feed those rounds' validation), --device_cache_gb (the
+training rounds' train_segnet.py --device_cache_gb, passed only when given), --label_loader_procs (the
 labelling passes' labels_from_segnet.py --loader_procs: decode workers per labelling process, independent of
 --loader_procs; the job needs n_gpus x label_loader_procs CPUs for them), --n_labels (overrides the
 split's constant), --no_figure (the labellers' 3-panel figures), --figure_renderer (labels_from_segnet.py's: matplotlib,
@@ -107,6 +108,9 @@ def get_parser():
     parser.add_argument('--loader_procs', type=int, default=0,
                         help="train_segnet.py --loader_procs for the training rounds: decode workers PER RANK "
                              "(keep n_gpus x loader_procs within the CPUs the job has); 0: none")
+    parser.add_argument('--device_cache_gb', type=float, default=0.0,
+                        help="train_segnet.py --device_cache_gb for the training rounds (needs --loader_procs): GB of "
+                             "decoded examples every rank keeps in device memory; the labelling passes do not take it")
     parser.add_argument('--label_loader_procs', type=int, default=0,
                         help="labels_from_segnet.py --loader_procs for the labelling passes: decode workers PER "
                              "LABELLING PROCESS; the job needs n_gpus x label_loader_procs CPUs for the decode workers; "
@@ -234,6 +238,8 @@ def train_argv(args, step, result_dir, dirs):
         a.append('--fused_bn')
     if args.loader_procs:
         a += ['--loader_procs', str(args.loader_procs)]
+    if args.device_cache_gb:
+        a += ['--device_cache_gb', repr(float(args.device_cache_gb))]
     return a
 
 
