@@ -432,12 +432,16 @@ class Engine(object):
         """(Cout,Cin,3,3) -> (n*n,Cout,Cin) float32: G g G^T of F(tile x tile, 3x3), computed in float64, position-major.
         tile 2: points 0, 1, -1, inf (n = 4); tile 4: points 0, 1, -1, 1/2, -2, inf (n = 6; csrc/spa_wino.hip)."""
         if tile == 2:
-            G = [[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]]
+            G, den = [[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], 1.0
         else:
-            G = [[1 / 2, 0, 0], [1 / 6, 1 / 6, 1 / 6], [1 / 6, -1 / 6, 1 / 6], [16 / 15, 8 / 15, 4 / 15],
-                 [1 / 30, -1 / 15, 2 / 15], [0, 0, 1 / 2]]
+            # 30 G, an integer matrix, and ONE division by 900 at the end: the thirds and fifteenths of G = (1/2, 0, 0), (1/6, 1/6, 1/6),
+            # (1/6, -1/6, 1/6), (16/15, 8/15, 4/15), (1/30, -1/15, 2/15), (0, 0, 1/2) are not float64 numbers, and with them as factors
+            # taps that cancel exactly left 1e-15 where U is zero (tests/wino_exact.py, premise (a))
+            G, den = [[15, 0, 0], [5, 5, 5], [5, -5, 5], [32, 16, 8], [1, -2, 4], [0, 0, 15]], 900.0
         G = torch.tensor(G, dtype=torch.float64, device=weight.device)
         u = torch.einsum('ij,kcjl,ml->imkc', G, weight.detach().double(), G)
+        if den != 1.0:
+            u.div_(den)
         return u.reshape(G.shape[0] ** 2, weight.shape[0], weight.shape[1]).float().contiguous()
 
     def conv3x3_wino_f32(self, x, u, bias, residual=None, relu=True, dilation=1, out=None, scratch=None):

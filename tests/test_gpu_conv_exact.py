@@ -8,8 +8,8 @@ shapes that reach the branch named beside them; test_conv_exact_cpu.py checks ea
 Covered: spa_conv3x3_bf16 (k_conv3x3_bf16 at the 64 and 128 tiles, k_conv3x3_bf16_stag), spa_conv_bf16_light (every instantiation),
 spa_conv3x3_f16s / spa_conv1x1_f16s (k_conv3x3_p16, k_conv3x3_f32<SPLIT>), spa_conv3x3_s2_f16s (k_conv3x3_s2_tile and the generic
 kernel), and one 'wide' case each of spa_conv3x3_f32 / spa_conv1x1_f32, spa_conv3x3_s2_f32, spa_conv_small_f16s, spa_drn_layer2_f32
-and spa_drn_layer2_f16s.  Left out because their arithmetic is not exact on integers: the Winograd paths (fractional transform
-points, per-position scales) and the fused stems (mean / std normalisation)."""
+and spa_drn_layer2_f16s.  The Winograd paths have tests/test_gpu_wino_exact.py; left out because their arithmetic is not exact
+on integers: the fused stems (mean / std normalisation)."""
 import importlib
 import os
 import sys
