@@ -12,12 +12,15 @@ Under `python -m torch.distributed.run --nproc-per-node N` the labelled driver s
 range like utils/create_*_labels.sh does and rank 0 writes result.json after one all_gather.
 """
 import argparse
+import collections
 import glob
 import json
 import os
 import sys
+import threading
 import time
 import zipfile
+from concurrent.futures import ThreadPoolExecutor
 
 # skip MIOpen's naive reference convolution during solver search (slow start-up, never selected)
 os.environ.setdefault('MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD', '0')
@@ -30,6 +33,7 @@ from . import dist as spdist
 from . import figure
 from . import ops
 from . import png
+from .engine import Engine
 from .pipeline import LabelPipeline
 from .slabs import Layout, PinnedSlabs, ShmTooSmall, Slabs, open_or_none
 
@@ -291,6 +295,12 @@ class ProcessDecoder(object):
         self.slabs.close()
 
 
+def _indices(n, lo, hi):
+    """The indices of dataset[lo:hi] in a dataset of n items (Python slice semantics, a negative lo included), without
+    building the n-element list: range(lo, min(hi, n)) for 0 <= lo."""
+    return range(n)[lo:hi]
+
+
 class ImageList(object):
     """ResizeImageDataset (datasets/resize_image_dataset.py:8-36): path -> CHW array."""
 
@@ -300,9 +310,12 @@ class ImageList(object):
     def __len__(self):
         return len(self._paths)
 
+    def _source(self, i):
+        """what _decode opens for image i: its path, or the open member of a zipped dataset"""
+        return self._open(self._paths[i]) if self._open else self._paths[i]
+
     def get(self, i):
-        src = self._open(self._paths[i]) if self._open else self._paths[i]
-        img = _decode(src)
+        img = _decode(self._source(i))
         if img.ndim == 2:
             img = img[:, :, None]
         img = img[:, :, :3].transpose(2, 0, 1)
@@ -312,16 +325,14 @@ class ImageList(object):
 
     def get_raw(self, i):
         """The decoded image as it comes out of the PNG decoder: (H, W, 3) uint8, not resized."""
-        src = self._open(self._paths[i]) if self._open else self._paths[i]
-        img = _decode(src)
+        img = _decode(self._source(i))
         if img.ndim == 2:
             img = img[:, :, None]
         return np.ascontiguousarray(img[:, :, :3])
 
     def get_gray(self, i):
         """A single-channel PNG (gtFine labelIds) as it is decoded: (H, W) uint8."""
-        src = self._open(self._paths[i]) if self._open else self._paths[i]
-        img = _decode(src)
+        img = _decode(self._source(i))
         return np.ascontiguousarray(img if img.ndim == 2 else img[:, :, 0])
 
     def batch_device(self, lo, hi, pool, engine, ring=None, want_u8=False):
@@ -329,7 +340,7 @@ class ImageList(object):
         8-bit images (3 bytes per pixel) and resize on the GPU (spa_resize_bicubic_u8: bit exact with the
         Pillow resize of `get`).  Falls back to `batch` when the images of the batch differ in size.
         want_u8: -> (that batch, the uploaded full-size (B,H,W,3) uint8 batch or None after the fall-back)."""
-        idx = list(range(len(self))[lo:hi])
+        idx = _indices(len(self), lo, hi)
         raw = list(pool.map(self.get_raw, idx)) if pool is not None else [self.get_raw(i) for i in idx]
         if len({r.shape for r in raw}) != 1 or raw[0].shape[2] != 3:
             # images of different sizes (or greyscale, which stays one channel like the reference's dataset):
@@ -353,7 +364,7 @@ class ImageList(object):
     def batch(self, lo, hi, pool=None):
         """dataset[lo:hi] stacked (python slice semantics, like concat_examples(dataset[i:end_i]));
         decoded by `pool` threads when given (PIL and numpy release the GIL)."""
-        idx = list(range(len(self))[lo:hi])
+        idx = _indices(len(self), lo, hi)
         imgs = list(pool.map(self.get, idx)) if pool is not None else [self.get(i) for i in idx]
         return np.stack(imgs)
 
@@ -397,13 +408,8 @@ def resize_nearest(a, shape):
 def score(road_mask, gt):
     """:398-405 — chainercv confusion/IoU on the host copy (integer counts: exact)."""
     m = gt >= 0
-    conf = np.bincount(2 * gt[m].astype(np.int64) + road_mask[m].astype(np.int64), minlength=4).reshape(2, 2)
-    TP, FP, FN = int(conf[1, 1]), int(conf[0, 1]), int(conf[1, 0])
-    with np.errstate(divide='ignore', invalid='ignore'):
-        iou = np.diag(conf) / (conf.sum(1) + conf.sum(0) - np.diag(conf))
-    return dict(road_iou=float(iou[1]), non_road_iou=float(iou[0]),
-                precision=float(TP / (TP + FP)) if TP + FP > 0 else None,
-                recall=float(TP / (TP + FN)) if TP + FN > 0 else None, TP=TP, FP=FP, FN=FN)
+    conf = np.bincount(2 * gt[m].astype(np.int64) + road_mask[m].astype(np.int64), minlength=4)
+    return score_from_counts(*(int(v) for v in conf))          # [TN, FP, FN, TP]
 
 
 def score_from_counts(TN, FP, FN, TP):
@@ -499,8 +505,379 @@ def append_result_line(path, line):
         os.close(fd)
 
 
+def _settle(eng, res, status_h, fail_h):
+    """A batch of an asynchronous loop whose status word (and k = 2 retry flags, where it has them) have reached the host:
+    raise what the device latched for it, then make the pipeline's retry check."""
+    eng.raise_on_word(status_h)
+    if fail_h is not None:
+        res.check_retry(fail_h)
+    elif getattr(res, 'retry_info', None) is not None:
+        res.check_retry()                 # k > 2 on the device: retry runs made / still pending
+
+
+Batch = collections.namedtuple('Batch', 'imgs ready gts gt_dev u8')
+
+
+class BatchLoader(object):
+    """The labelled driver's input stage: the batches of `ranges`, loaded by two threads ahead of the loop that takes them
+    with next(), in range order (decode and resize of the NEXT batch run while the GPU labels the
+    current one): two batches ahead in the asynchronous loop, one otherwise.
+    On the GPU the frames are decoded on the worker threads (or by the --decode_procs processes) and resized on the device
+    (bit exact with the host resize), each loader thread with its own spa_ctx, stream and pinned rings: a context's
+    workspaces serve one caller at a time, so a loader thread shares none with the pipeline's thread or the other loader."""
+
+    def __init__(self, args, imgs_ds, labels_ds, ranges, workers, renderer, use_async, have_gpu):
+        self.args, self.imgs_ds, self.labels_ds, self.ranges, self.workers = args, imgs_ds, labels_ds, ranges, workers
+        self.renderer, self.use_async, self.have_gpu = renderer, use_async, have_gpu
+        self.tls, self.decoder, self.decoder_lock = threading.local(), None, threading.Lock()
+        if use_async and have_gpu and getattr(args, 'decode_procs', 0) > 0 and not args.host_resize and ranges:
+            self.decoder = open_or_none(lambda: ProcessDecoder(imgs_ds, labels_ds, args.batchsize, args.decode_procs,
+                                                               ops.engine().device, host_labels=not args.no_figure),
+                                        '--decode_procs: %%s; decoding on the %d io threads instead' % args.io_threads, sys.stderr)
+            if self.decoder is not None and renderer == 'device' and self.decoder.ishape[:2] == self.decoder.gshape:
+                self.decoder.host_labels = False         # every batch it delivers gets its figures on the device
+        depth = 2 if use_async else 1
+        self.pool = ThreadPoolExecutor(max_workers=2)
+        self.queue, self.todo = [self.pool.submit(self._load, lo, hi) for lo, hi in ranges[:depth]], list(ranges[depth:])
+
+    def next(self):
+        """The next batch of `ranges`; the load that is `depth` ahead of it is submitted right away."""
+        batch = self.queue.pop(0).result()
+        if self.todo:
+            self.queue.append(self.pool.submit(self._load, *self.todo.pop(0)))
+        return batch
+
+    def close(self):
+        self.pool.shutdown()
+        if self.decoder is not None:
+            self.decoder.close()
+
+    def _context(self):
+        """this loader thread's own (Engine, stream, frame ring, ground-truth ring)"""
+        tls = self.tls
+        if self.have_gpu and not hasattr(tls, 'eng'):
+            tls.eng = Engine(ops.engine().device.index)
+            tls.stream = torch.cuda.Stream(device=tls.eng.device)
+            tls.ring = PinnedRing()
+            tls.gt_ring = PinnedRing()
+        return tls
+
+    def _load(self, lo, hi):
+        """-> Batch: imgs at --resize_shape (a device tensor, or a host array where nothing was uploaded), `ready`: the
+        event recorded on this thread's stream behind everything enqueued for the batch (None: nothing in flight), and
+        for the asynchronous loop the ground truth on the host (gts) and on the device (gt_dev); u8: the full-size
+        uploaded frames where the figures are drawn on the device."""
+        args, imgs_ds, workers, tls = self.args, self.imgs_ds, self.workers, self._context()
+        idx = _indices(len(imgs_ds), lo, hi)
+        if self.decoder is not None:
+            # worker processes decode images and labels into a pinned shared-memory slab; one DMA each
+            # (one take at a time, under this thread's stream, where `ready` is recorded too)
+            with self.decoder_lock:
+                with torch.cuda.stream(tls.stream):
+                    got = self.decoder.take(idx)
+                    if got is not None:
+                        u8, gt_dev, gts = got
+                        shape = tuple(imgs_ds._shape) if imgs_ds._shape is not None else tuple(u8.shape[1:3])
+                        t = tls.eng.resize_u8(u8, shape, RESIZE_BACKEND[0])
+                        ev = torch.cuda.Event()
+                        ev.record(tls.stream)
+                        return Batch(t, ev, gts, gt_dev, u8)
+        # ground truth PNGs of the batch decode alongside its images
+        gt_f = [workers.submit(self.labels_ds.get_gray, i) for i in idx] if self.use_async else None
+        gts = gt_dev = ev = u8 = None
+        if self.have_gpu and not args.host_resize:
+            with torch.cuda.stream(tls.stream):
+                # (the figures on the device want the full-size batch that the resize read)
+                t, u8 = imgs_ds.batch_device(lo, hi, workers, tls.eng, tls.ring, want_u8=True)
+                if self.renderer != 'device':
+                    u8 = None
+        else:
+            t = imgs_ds.batch(lo, hi, workers)
+        if gt_f is not None:
+            gts = [f.result() for f in gt_f]
+            if len({g.shape for g in gts}) == 1:
+                with torch.cuda.stream(tls.stream):
+                    gt_dev = tls.gt_ring.upload(gts, tls.eng.device, workers)
+        if self.have_gpu and (isinstance(t, torch.Tensor) or gt_dev is not None):    # else: host arrays, nothing in flight
+            ev = torch.cuda.Event()
+            ev.record(tls.stream)
+        return Batch(t, ev, gts, gt_dev, u8)
+
+
+class ImageWriter(object):
+    """The labelled driver's output stage: the per-image outputs of the PREVIOUS batch (GT decode, nearest resize, two
+    .npy files, figure, scores, result line) run on the `workers` threads while the GPU labels the current one.
+    submit() queues one image, drain_all() collects what was queued, close() ends the run."""
+
+    def __init__(self, args, imgs_ds, labels_ds, single):
+        self.args, self.imgs_ds, self.labels_ds, self.single = args, imgs_ds, labels_ds, single
+        self.workers = ThreadPoolExecutor(max_workers=max(1, args.io_threads))
+        self.path = os.path.join(args.out_dir, 'result.json')
+        self.pending = []           # futures of the images queued since the last drain_all()
+        self.keep = []              # what holds the pinned buffers that the writers of `pending` read from
+        self.drained = set()
+        self.records, self.own = [], {}     # per finished image: its fixed-size record for the gather, its line by index
+
+    def finish(self, i, rm, cl, n_sp, info, times, st_all, conf=None, gt_raw=None, fig=None):
+        """Everything the reference does per image after the masks exist (:461-483, :388-424).  conf: the
+        image's {TN, FP, FN, TP} already counted on the device against its ground truth, with rm / cl already at
+        the ground truth's size (the asynchronous loop); otherwise decode, resize and count here.  fig: (figures, slot,
+        j) of the image's overview figure encoded on the device (--figure_renderer device): <stem>.jpg."""
+        args, imgs_ds = self.args, self.imgs_ds
+        img_fn, label_fn = imgs_ds._paths[i], self.labels_ds._paths[i]
+        if conf is not None:
+            save_npy(args, img_fn, rm, cl)
+            if fig is not None:
+                png.write_file(os.path.join(args.out_dir, os.path.splitext(os.path.basename(img_fn))[0] + '.jpg'),
+                               fig[0].file_bytes(fig[1], fig[2]))
+            elif not args.no_figure:
+                save_figure(args, _decode(imgs_ds._source(i)), rm, create_label_mask(gt_raw), cl, img_fn)   # :464 reloads the PNG
+            sc = score_from_counts(*(int(v) for v in conf))
+            tn = int(conf[0])
+        else:
+            gt = create_label_mask(self.labels_ds.get(i)[0] if gt_raw is None else gt_raw)
+            if rm.shape != gt.shape:                                       # :470-477
+                rm = resize_nearest(rm, gt.shape)
+            if cl.shape != gt.shape:
+                cl = resize_nearest(cl, gt.shape)
+            save_npy(args, img_fn, rm, cl)
+            if not args.no_figure:
+                save_figure(args, _decode(imgs_ds._source(i)), rm, gt, cl, img_fn)      # :464 reloads the PNG
+            sc = score(rm, gt)
+            tn = int(((gt == 0) & (rm == 0)).sum())
+        line = result_line(args, img_fn, label_fn, sc, times, st_all)
+        timers = dict(times, elapsed_time=line['elapsed_time'], gpu=args.gpu)
+        return i, line, [i, tn, sc['FP'], sc['FN'], sc['TP'], n_sp, int(info[0]), int(info[1])] \
+            + spdist.pack_timers(timers)
+
+    def submit(self, *finish_args):
+        self.pending.append(self.workers.submit(self.finish, *finish_args))
+
+    def _drain(self, futs):
+        """Collect finished images; a single process appends their result.json lines NOW (the
+        reference appends one line per image as it goes, :407-422), so a failure in a later batch
+        loses nothing already computed.  Under torchrun rank 0 writes after the gather instead."""
+        for f in futs:
+            if f in self.drained:
+                continue
+            i, line, rec = f.result()
+            self.drained.add(f)
+            self.records.append(rec)
+            self.own[i] = line
+            if self.single:
+                append_result_line(self.path, line)
+            print('Road IoU:', line['road_iou'], os.path.basename(line['img_fn']))
+
+    def drain_all(self):
+        """Both loops call this before they queue a batch's images: a re-labelled image (last batch shifted back,
+        :539-542) must overwrite its earlier files, so the previous batch's writers finish first.  `pending` keeps
+        them until they are drained, so that close() still sees the successful ones if one of them failed, and `keep`
+        holds their pinned buffers until then."""
+        self._drain(self.pending)
+        del self.pending[:]
+        del self.keep[:]
+
+    def close(self):
+        """Whatever was computed before an error (corrupt PNG, device status, OOM) still reaches disk: the successful
+        images are drained -> the first failed one's exception or None, for the caller to raise after its clean-up."""
+        bad = [f for f in self.pending if f.exception() is not None]
+        self._drain([f for f in self.pending if f.exception() is None])
+        self.workers.shutdown()
+        return bad[0].exception() if bad else None
+
+
+class LabelledFigures(object):
+    """--figure_renderer device in the labelled driver: one figure.DeviceFigures per ground-truth size, all in one
+    context of their own.  The JPEG kernels' workspace must not grow in the pipeline's context, where it would make the
+    captured DRN graph stale (drn.py, _graph_forward) and have it captured once more."""
+
+    def __init__(self, args, device):
+        self.batch, self.device = args.batchsize, device
+        self.luts = (figure.overlay(), figure.two_colour([7]), figure.clusters(max(args.n_clusters, 2)),
+                     figure.two_colour([0]))
+        self.modes = (figure.BLEND, figure.TABLE, figure.TABLE, figure.TABLE)
+        self.eng, self.by_shape, self.told = None, {}, False
+
+    def encode(self, u8, gt_dev, road_d, cl_d):
+        """on the current stream: the batch's 2x2 figures in matplotlib's panel order (the frame under the road
+        mask, the ground truth's road, all clusters, cluster 0) -> (figures, slot), or None where the batch's
+        ground truth is not on the device or its frames have another size: matplotlib draws those"""
+        if u8 is None or gt_dev is None or tuple(u8.shape[1:3]) != tuple(gt_dev.shape[1:]):
+            if not self.told:
+                self.told = True
+                print('--figure_renderer device: a batch whose ground truth is not on the device at the frames\' '
+                      'size gets matplotlib figures', file=sys.stderr)
+            return None
+        shape = tuple(gt_dev.shape[1:])
+        if shape not in self.by_shape:
+            if self.eng is None:
+                self.eng = Engine(self.device.index)
+            self.by_shape[shape] = figure.DeviceFigures(self.eng, shape, self.batch, (2, 2))
+        figs = self.by_shape[shape]
+        u8.record_stream(torch.cuda.current_stream(self.device))
+        road_c, cl_c = road_d.contiguous(), cl_d.contiguous()
+        return figs, figs.encode(u8, [road_c, gt_dev, cl_c, cl_c], self.luts, self.modes)
+
+    def close(self):
+        """The figures' context goes now, not whenever a collection finds it (drn.py, _graph_capture: a context freed
+        while a later call of main_labelled captures its graph invalidates the capture)."""
+        eng, self.eng = self.eng, None
+        self.by_shape.clear()
+        if eng is not None:
+            eng.close()
+
+
+class _AsyncLoop(object):
+    """main_labelled's loop for LabelPipeline on the GPU.  One batch of deferral: while the GPU labels batch k the host
+    finishes batch k-1 (status, timers from its device events, writers) and the loader decodes batch k+1 — the main
+    thread never waits for the batch it has just enqueued.  Scoring runs on the device (create_label_mask, nearest
+    resize to the ground truth's size, spa_confusion), so a worker only writes the two .npy files and the result line."""
+
+    def __init__(self, pipe, writer, figures):
+        self.pipe, self.writer, self.figures, self.eng = pipe, writer, figures, ops.engine()
+        self.d2h = torch.cuda.Stream(device=self.eng.device)
+        self.index_cache = {}
+
+    def to_gt_size(self, m, shape):
+        """(B, h, w) masks -> the ground truth's shape, as cv.INTER_NEAREST resizes them (resize_nearest, on the device)"""
+        if tuple(m.shape[1:]) == tuple(shape):
+            return m
+        key = (tuple(m.shape[1:]), tuple(shape))
+        if key not in self.index_cache:
+            self.index_cache[key] = (torch.from_numpy(nearest_index(shape[0], m.shape[1])).to(self.eng.device),
+                                     torch.from_numpy(nearest_index(shape[1], m.shape[2])).to(self.eng.device))
+        ys, xs = self.index_cache[key]
+        return m.index_select(1, ys).index_select(2, xs)
+
+    def enqueue(self, batch, idx, st_all):
+        """Everything of one batch that goes to the device before its results are looked at -> its state record."""
+        eng, (imgs, ready, gts, gt_dev, u8) = self.eng, batch
+        main = torch.cuda.current_stream()
+        if ready is not None:
+            # the hand-over from the loader thread's stream: wait first, then tell the allocator who reads the tensors
+            main.wait_event(ready)
+            for t in (imgs, gt_dev, u8):
+                if isinstance(t, torch.Tensor):
+                    t.record_stream(main)
+        # join=False: the batch's tail (pooling, k-means, paint) runs on the pipeline's second stream and this stream goes
+        # straight on to the next batch's DRN forward; everything below is enqueued where the result lives (res.stream)
+        res = self.pipe.run(imgs, check_status=False, join=False)
+        events = dict(self.pipe._ev)
+        with torch.cuda.stream(res.stream):
+            road_d, cl_d, conf_d = res.road, res.cluster, None
+            if gt_dev is not None:
+                gt_dev.record_stream(res.stream)
+                road_d, cl_d = self.to_gt_size(res.road, gt_dev.shape[1:]), self.to_gt_size(res.cluster, gt_dev.shape[1:])
+                gtm = torch.where(gt_dev <= 6, -1, torch.where(gt_dev == 7, 1, 0)).to(torch.int32)   # :279-296
+                conf_d = eng.confusion(road_d.contiguous(), gtm)
+            fig = self.figures.encode(u8, gt_dev, road_d, cl_d) if self.figures is not None else None
+            status_h = eng.status_take_async()          # the bits raised so far (one atomic exchange, in stream order)
+            computed = torch.cuda.Event(enable_timing=True)
+            computed.record(res.stream)
+        # the downloads are enqueued by finalize(), once the batch HAS been computed (the host waits, the copy stream does
+        # not): a copy queue whose head is a barrier waiting a batch's time for the compute stream slows every dispatch of
+        # that batch (measured: 82 -> 77.6 ms per batch of 30 in pipeline.HostStream, tools/h2h_probe2.py)
+        return dict(idx=idx, res=res, events=events, gts=gts, st_all=st_all, status_h=status_h, computed=computed,
+                    dev=(road_d, cl_d, conf_d), fig=fig)
+
+    def finalize(self, st):
+        """Wait for the batch, download its results on the copy stream, settle its status and queue its images' writers."""
+        res, d2h, writer = st['res'], self.d2h, self.writer
+        road_d, cl_d, conf_d = st.pop('dev')
+        st['computed'].synchronize()
+        with torch.cuda.stream(d2h):
+            host = []
+            for d, dtype in ((road_d, torch.uint8), (cl_d, torch.uint8), (res.info, None), (res.n_labels, None),
+                             (conf_d, None), (res.retry_fail, torch.bool)):
+                host.append(None if d is None else torch.empty(d.shape, dtype=dtype or d.dtype, pin_memory=True))
+                if d is not None:
+                    host[-1].copy_(d, non_blocking=True)
+                    d.record_stream(d2h)
+            done = torch.cuda.Event()
+            done.record(d2h)
+        done.synchronize()
+        st['host'] = host                   # `keep` holds the pinned buffers until the writers are through
+        road_h, cl_h, info_h, nsp_h, conf_h, fail_h = host
+        _settle(self.eng, res, st['status_h'], fail_h)
+        times = self.pipe.elapsed_times(st['events'])
+        # `elapsed_time` stays what the reference reports (:420: wall clock since the batch was started, which in this
+        # loop includes the batches in flight ahead of it); the batch's own device time goes under its own key
+        times['time_device'] = st['events']['start'].elapsed_time(st['computed']) / 1000.0
+        info, n_sp = info_h.numpy(), nsp_h.numpy()
+        conf = conf_h.numpy() if conf_h is not None else None
+        writer.drain_all()                  # before this batch's writers are queued: see there
+        writer.keep.append(st)
+        fig = st['fig']
+        if fig is not None:
+            fig[0].fetch(fig[1])            # the used bytes of the batch's JPEG scans; the writers wait for them
+        for j, i in enumerate(st['idx']):
+            writer.submit(i, road_h[j].numpy(), cl_h[j].numpy(), int(n_sp[j]), info, times, st['st_all'],
+                          None if conf is None else conf[j], None if st['gts'] is None else st['gts'][j],
+                          None if fig is None else fig + (j,))
+
+    def run(self, loader, n_data):
+        prev = None
+        trace = os.environ.get('SPA_DRIVER_TRACE') == '1'      # host-side timeline of the loop, one line per batch
+        for bi, (lo, hi) in enumerate(loader.ranges):
+            st_all = time.time()
+            batch = loader.next()
+            t_loaded = time.time()
+            st = self.enqueue(batch, _indices(n_data, lo, hi), st_all)
+            t_enq = time.time()
+            if prev is not None:                # finalize runs one batch behind: batch k is on the device by now
+                self.finalize(prev)
+                if trace:
+                    print('trace batch %d: wait_load %.1f ms, enqueue %.1f ms, finalize(prev) %.1f ms, device batch(prev) '
+                          '%.1f ms' % (bi, (t_loaded - st_all) * 1e3, (t_enq - t_loaded) * 1e3, (time.time() - t_enq) * 1e3,
+                                       prev['events']['start'].elapsed_time(prev['computed'])), file=sys.stderr)
+            prev = st
+        if prev is not None:
+            self.finalize(prev)
+
+
+def _simple_loop(pipe, loader, writer, n_data, orig_ds):
+    """main_labelled's synchronous loop (the baselines, the stub model of the host tests, any `make_pipe`): a batch's
+    results are fetched as soon as it has run; only the loader (one batch ahead) and the writers overlap it.
+    orig_ds: the pipeline also gets the undecimated uint8 images of the batch."""
+    for lo, hi in loader.ranges:
+        st_all = time.time()
+        imgs, ready = loader.next()[:2]
+        if ready is not None:
+            torch.cuda.current_stream().wait_event(ready)
+            if isinstance(imgs, torch.Tensor):
+                imgs.record_stream(torch.cuda.current_stream())
+        res = pipe.run(imgs, orig_ds.batch(lo, hi, writer.workers)) if orig_ds is not None else pipe.run(imgs)
+        times = pipe.elapsed_times()
+        cluster, road = res.masks_to_host()
+        info = res.info.cpu().numpy()
+        n_sp = res.n_labels.cpu().numpy()
+        writer.drain_all()                  # before this batch's writers are queued: see there
+        for j, i in enumerate(_indices(n_data, lo, hi)):
+            writer.submit(i, road[j], cluster[j], int(n_sp[j]), info, times, st_all)
+
+
+def _write_gathered_lines(args, imgs_ds, labels_ds, writer, rank):
+    """Several ranks.  One collective: fixed-size records (scores + the stage timers of the image's batch); rank 0
+    writes result.json in index order and rebuilds the lines it did not produce from the records (file names come
+    from the shared lists)."""
+    allrec = spdist.gather_records(np.array(writer.records, np.int64).reshape(-1, spdist.RECORD_WIDTH))
+    if rank == 0:
+        order = np.argsort(allrec[:, 0], kind='stable') if len(allrec) else []
+        for r in allrec[order]:                                     # index order
+            i = int(r[0])
+            line = writer.own.get(i)
+            if line is None:
+                sc = score_from_counts(*(int(v) for v in r[1:5]))    # TN, FP, FN, TP
+                timers = spdist.unpack_timers(r)
+                line = result_line(args, imgs_ds._paths[i], labels_ds._paths[i], sc, {}, time.time())
+                line['gpu'] = int(timers.pop('gpu', args.gpu))
+                line.update(timers)                                  # time_* and elapsed_time of its rank
+            append_result_line(writer.path, line)
+    spdist.barrier()
+
+
 def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_model=None):
-    """The labelled driver loop.  `get` / `make_pipe` select one of the three scripts that share it
+    """The labelled driver.  `get` / `make_pipe` select one of the three scripts that share it
     (batch_spalign_kmeans.py, direct_clustering.py, superpixel_overlaps.py); `originals`: the
     pipeline also wants the undecimated uint8 images of the batch (superpixel_overlaps.py:322);
     `make_model`: factory replacing create_model (tests of the host logic inject a stub)."""
@@ -520,339 +897,32 @@ def main_labelled(argv=None, get=None, make_pipe=None, originals=False, make_mod
     if ws > 1:
         s, e = spdist.shard_range(end - start, ws, rank, args.balanced)
         start, end = start + s, start + e
-    # Host side of the loop: decode/resize of the NEXT batch and the per-image
-    # outputs of the PREVIOUS one (GT decode, nearest resize, two .npy files, figure, scores) run on
-    # worker threads while the GPU labels the current batch.
-    from concurrent.futures import ThreadPoolExecutor
-    workers = ThreadPoolExecutor(max_workers=max(1, args.io_threads))
-    loader = ThreadPoolExecutor(max_workers=2)     # two batches ahead in the asynchronous loop, one otherwise
     # a range shorter than one batch that starts at image 0 makes the reference slice dataset[-k:end],
     # which is empty, and crash in concat_examples; here that range is labelled as one smaller batch
     ranges = [(max(lo, 0), hi) for lo, hi in spdist.batch_ranges(start, end, args.batchsize)] if end > start else []
-    path = os.path.join(args.out_dir, 'result.json')
-
-    def finish(i, rm, cl, n_sp, info, times, st_all, conf=None, gt_raw=None, fig=None):
-        """Everything the reference does per image after the masks exist (:461-483, :388-424).  conf: the
-        image's {TN, FP, FN, TP} already counted on the device against its ground truth, with rm / cl already at
-        the ground truth's size (the asynchronous loop); otherwise decode, resize and count here.  fig: (figures, slot,
-        j) of the image's overview figure encoded on the device (--figure_renderer device): <stem>.jpg."""
-        img_fn, label_fn = imgs_ds._paths[i], labels_ds._paths[i]
-        if conf is not None:
-            save_npy(args, img_fn, rm, cl)
-            gt = None
-            if fig is not None:
-                png.write_file(os.path.join(args.out_dir, os.path.splitext(os.path.basename(img_fn))[0] + '.jpg'),
-                               fig[0].file_bytes(fig[1], fig[2]))
-            elif not args.no_figure:
-                gt = create_label_mask(gt_raw)
-                full = _decode(imgs_ds._open(img_fn) if imgs_ds._open else img_fn)   # :464 reloads the PNG
-                save_figure(args, full, rm, gt, cl, img_fn)
-            sc = score_from_counts(*(int(v) for v in conf))
-            tn = int(conf[0])
-        else:
-            gt = create_label_mask(labels_ds.get(i)[0] if gt_raw is None else gt_raw)
-            if rm.shape != gt.shape:                                       # :470-477
-                rm = resize_nearest(rm, gt.shape)
-            if cl.shape != gt.shape:
-                cl = resize_nearest(cl, gt.shape)
-            save_npy(args, img_fn, rm, cl)
-            if not args.no_figure:
-                full = _decode(imgs_ds._open(img_fn) if imgs_ds._open else img_fn)   # :464 reloads the PNG
-                save_figure(args, full, rm, gt, cl, img_fn)
-            sc = score(rm, gt)
-            tn = int(((gt == 0) & (rm == 0)).sum())
-        line = result_line(args, img_fn, label_fn, sc, times, st_all)
-        timers = dict(times, elapsed_time=line['elapsed_time'], gpu=args.gpu)
-        return i, line, [i, tn, sc['FP'], sc['FN'], sc['TP'], n_sp, int(info[0]), int(info[1])] \
-            + spdist.pack_timers(timers)
-
-    records = []
-    own = {}
-    drained = set()
-
-    def drain(futs):
-        """Collect finished images; a single process appends their result.json lines NOW (the
-        reference appends one line per image as it goes, :407-422), so a failure in a later batch
-        loses nothing already computed.  Under torchrun rank 0 writes after the gather instead."""
-        for f in futs:
-            if f in drained:
-                continue
-            i, line, rec = f.result()
-            drained.add(f)
-            records.append(rec)
-            own[i] = line
-            if ws == 1:
-                append_result_line(path, line)
-            print('Road IoU:', line['road_iou'], os.path.basename(line['img_fn']))
-
-    pending = []
-    keep = []               # pinned buffers the writers of `pending` read from
-    decoder = None
-    figures = {}            # --figure_renderer device: figure.DeviceFigures per ground-truth size, and their context 'eng'
     # the asynchronous loop: LabelPipeline on the GPU (the baselines and the stub-model tests keep the simple one)
-    use_async = make_pipe is None and make_model is None
+    use_async, have_gpu = make_pipe is None and make_model is None, make_model is None
+    writer = ImageWriter(args, imgs_ds, labels_ds, ws == 1)
+    figures = LabelledFigures(args, ops.engine().device) if use_async and renderer == 'device' else None
+    loader = None
     try:
-        # GPU input stage: decode on the worker threads, resize on the device (bit exact with the host resize)
-        # (its own spa_ctx: the loader thread must not share a context with the pipeline's thread)
-        from .engine import Engine
-        import threading
-        have_gpu = make_model is None
-        tls = threading.local()         # one spa_ctx + one stream per loader thread (a context's workspaces serve
-        #                                 one caller at a time), pinned rings likewise
-
-        def load(lo, hi):
-            idx = list(range(len(imgs_ds)))[lo:hi]
-            if have_gpu and not hasattr(tls, 'eng'):
-                tls.eng = Engine(ops.engine().device.index)
-                tls.stream = torch.cuda.Stream(device=tls.eng.device)
-                tls.ring = PinnedRing()
-                tls.gt_ring = PinnedRing()
-            if decoder is not None:
-                # worker processes decode images and labels into a pinned shared-memory slab; one DMA each
-                with decoder_lock:
-                    with torch.cuda.stream(tls.stream):
-                        got = decoder.take(idx)
-                        if got is not None:
-                            u8, gt_dev, gts = got
-                            shape = tuple(imgs_ds._shape) if imgs_ds._shape is not None else tuple(u8.shape[1:3])
-                            t = tls.eng.resize_u8(u8, shape, RESIZE_BACKEND[0])
-                            ev = torch.cuda.Event()
-                            ev.record(tls.stream)
-                            return t, ev, gts, gt_dev, u8
-            # ground truth PNGs of the batch decode alongside its images
-            gt_f = [workers.submit(labels_ds.get_gray, i) for i in idx] if use_async else None
-            gts = gt_dev = ev = u8 = None
-            if have_gpu and not args.host_resize:
-                with torch.cuda.stream(tls.stream):
-                    # (the figures on the device want the full-size batch that the resize read)
-                    t, u8 = imgs_ds.batch_device(lo, hi, workers, tls.eng, tls.ring, want_u8=True)
-                    if renderer != 'device':
-                        u8 = None
-            else:
-                t = imgs_ds.batch(lo, hi, workers)
-            if gt_f is not None:
-                gts = [f.result() for f in gt_f]
-                if len({g.shape for g in gts}) == 1:
-                    with torch.cuda.stream(tls.stream):
-                        gt_dev = tls.gt_ring.upload(gts, tls.eng.device, workers)
-            if have_gpu and (isinstance(t, torch.Tensor) or gt_dev is not None):    # else: host arrays, nothing in flight
-                ev = torch.cuda.Event()
-                ev.record(tls.stream)
-            return t, ev, gts, gt_dev, u8
-
-        def drain_all():
-            drain(pending)
-            del pending[:]
-            del keep[:]
-
-        decoder_lock = threading.Lock()
-        if use_async and have_gpu and getattr(args, 'decode_procs', 0) > 0 and not args.host_resize and ranges:
-            decoder = open_or_none(lambda: ProcessDecoder(imgs_ds, labels_ds, args.batchsize, args.decode_procs,
-                                                          ops.engine().device, host_labels=not args.no_figure),
-                                   '--decode_procs: %%s; decoding on the %d io threads instead' % args.io_threads, sys.stderr)
-            if decoder is not None and renderer == 'device' and decoder.ishape[:2] == decoder.gshape:
-                decoder.host_labels = False         # every batch it delivers gets its figures on the device
-        depth = 2 if use_async else 1
-        queue = [loader.submit(load, lo, hi) for lo, hi in ranges[:depth]]
+        loader = BatchLoader(args, imgs_ds, labels_ds, ranges, writer.workers, renderer, use_async, have_gpu)
         if use_async:
-            # One batch of deferral: while the GPU labels batch k the host finishes batch k-1 (status, timers from
-            # its device events, writers) and decodes batch k+1 — the main thread never waits for the batch it
-            # has just enqueued.  Scoring runs on the device (create_label_mask, nearest resize to the ground
-            # truth's size, spa_confusion), so a worker only writes the two .npy files and the result line.
-            eng = ops.engine()
-            dev = eng.device
-            d2h = torch.cuda.Stream(device=dev)
-            index_cache = {}
-
-            def to_gt_size(m, shape):
-                if tuple(m.shape[1:]) == tuple(shape):
-                    return m
-                key = (tuple(m.shape[1:]), tuple(shape))
-                if key not in index_cache:
-                    index_cache[key] = (torch.from_numpy(nearest_index(shape[0], m.shape[1])).to(dev),
-                                        torch.from_numpy(nearest_index(shape[1], m.shape[2])).to(dev))
-                ys, xs = index_cache[key]
-                return m.index_select(1, ys).index_select(2, xs)
-
-            fig_luts = (figure.overlay(), figure.two_colour([7]), figure.clusters(max(args.n_clusters, 2)),
-                        figure.two_colour([0]))
-            fig_modes = (figure.BLEND, figure.TABLE, figure.TABLE, figure.TABLE)
-            told = []
-
-            def encode_figures(u8, gt_dev, road_d, cl_d):
-                """on the current stream: the batch's 2x2 figures in matplotlib's panel order (the frame under the road
-                mask, the ground truth's road, all clusters, cluster 0) -> (figures, slot), or None where the batch's
-                ground truth is not on the device or its frames have another size: matplotlib draws those"""
-                if u8 is None or gt_dev is None or tuple(u8.shape[1:3]) != tuple(gt_dev.shape[1:]):
-                    if not told:
-                        told.append(True)
-                        print('--figure_renderer device: a batch whose ground truth is not on the device at the frames\' '
-                              'size gets matplotlib figures', file=sys.stderr)
-                    return None
-                shape = tuple(gt_dev.shape[1:])
-                if shape not in figures:
-                    # a context of its own: the JPEG kernels' workspace must not grow in the pipeline's context, where it
-                    # would make the captured DRN graph stale (drn.py, _graph_forward) and have it captured once more
-                    if 'eng' not in figures:
-                        figures['eng'] = Engine(dev.index)
-                    figures[shape] = figure.DeviceFigures(figures['eng'], shape, args.batchsize, (2, 2))
-                u8.record_stream(torch.cuda.current_stream(dev))
-                road_c, cl_c = road_d.contiguous(), cl_d.contiguous()
-                return figures[shape], figures[shape].encode(u8, [road_c, gt_dev, cl_c, cl_c], fig_luts, fig_modes)
-
-            def finalize(st):
-                res = st['res']
-                road_d, cl_d, conf_d = st.pop('dev')
-                st['computed'].synchronize()
-                with torch.cuda.stream(d2h):
-                    st.update(road_h=torch.empty(road_d.shape, dtype=torch.uint8, pin_memory=True),
-                              cl_h=torch.empty(cl_d.shape, dtype=torch.uint8, pin_memory=True),
-                              info_h=torch.empty(res.info.shape, dtype=res.info.dtype, pin_memory=True),
-                              nsp_h=torch.empty(res.n_labels.shape, dtype=res.n_labels.dtype, pin_memory=True),
-                              conf_h=None if conf_d is None else torch.empty(conf_d.shape, dtype=conf_d.dtype, pin_memory=True),
-                              fail_h=None if res.retry_fail is None else torch.empty(res.retry_fail.shape, dtype=torch.bool, pin_memory=True))
-                    for h, d in ((st['road_h'], road_d), (st['cl_h'], cl_d), (st['info_h'], res.info),
-                                 (st['nsp_h'], res.n_labels), (st['conf_h'], conf_d), (st['fail_h'], res.retry_fail)):
-                        if h is not None:
-                            h.copy_(d, non_blocking=True)
-                            d.record_stream(d2h)
-                    st['done'] = torch.cuda.Event()
-                    st['done'].record(d2h)
-                st['done'].synchronize()
-                eng.raise_on_word(st['status_h'])
-                if st['fail_h'] is not None:
-                    st['res'].check_retry(st['fail_h'])
-                elif getattr(st['res'], 'retry_info', None) is not None:
-                    st['res'].check_retry()                 # k > 2 on the device: retry runs made / still pending
-                times = pipe.elapsed_times(st['events'])
-                # `elapsed_time` stays what the reference reports (:420: wall clock since the batch was started, which in this
-                # loop includes the batches in flight ahead of it); the batch's own device time goes under its own key
-                times['time_device'] = st['events']['start'].elapsed_time(st['computed']) / 1000.0
-                info, n_sp = st['info_h'].numpy(), st['nsp_h'].numpy()
-                conf = st['conf_h'].numpy() if st['conf_h'] is not None else None
-                # a re-labelled image (last batch shifted back, :539-542) must overwrite its earlier files:
-                # the previous batch's writers finish before this batch's are queued
-                drain_all()
-                keep.append(st)
-                fig = st['fig']
-                if fig is not None:
-                    fig[0].fetch(fig[1])            # the used bytes of the batch's JPEG scans; the writers wait for them
-                for j, i in enumerate(st['idx']):
-                    pending.append(workers.submit(finish, i, st['road_h'][j].numpy(), st['cl_h'][j].numpy(), int(n_sp[j]),
-                                                  info, times, st['st_all'],
-                                                  None if conf is None else conf[j],
-                                                  None if st['gts'] is None else st['gts'][j],
-                                                  None if fig is None else fig + (j,)))
-
-            prev = None
-            trace = os.environ.get('SPA_DRIVER_TRACE') == '1'      # host-side timeline of the loop, one line per batch
-            for bi, (lo, hi) in enumerate(ranges):
-                st_all = time.time()
-                imgs, ready, gts, gt_dev, u8 = queue.pop(0).result()
-                if bi + depth < len(ranges):
-                    queue.append(loader.submit(load, ranges[bi + depth][0], ranges[bi + depth][1]))
-                t_loaded = time.time()
-                main = torch.cuda.current_stream()
-                if ready is not None:
-                    main.wait_event(ready)
-                    for t in (imgs, gt_dev, u8):
-                        if isinstance(t, torch.Tensor):
-                            t.record_stream(main)
-                # join=False: the batch's tail (pooling, k-means, paint) runs on the pipeline's second stream and this stream goes
-                # straight on to the next batch's DRN forward; everything below is enqueued where the result lives (res.stream)
-                res = pipe.run(imgs, check_status=False, join=False)
-                events = dict(pipe._ev)
-                with torch.cuda.stream(res.stream):
-                    road_d, cl_d, conf_d = res.road, res.cluster, None
-                    if gt_dev is not None:
-                        gt_dev.record_stream(res.stream)
-                        road_d, cl_d = to_gt_size(res.road, gt_dev.shape[1:]), to_gt_size(res.cluster, gt_dev.shape[1:])
-                        gtm = torch.where(gt_dev <= 6, -1, torch.where(gt_dev == 7, 1, 0)).to(torch.int32)   # :279-296
-                        conf_d = eng.confusion(road_d.contiguous(), gtm)
-                    fig = encode_figures(u8, gt_dev, road_d, cl_d) if renderer == 'device' else None
-                    status_h = eng.status_take_async()          # the bits raised so far (one atomic exchange, in stream order)
-                    computed = torch.cuda.Event(enable_timing=True)
-                    computed.record(res.stream)
-                # the downloads are enqueued by finalize(), once the batch HAS been computed (the host waits, the copy stream does
-                # not): a copy queue whose head is a barrier waiting a batch's time for the compute stream slows every dispatch of
-                # that batch (measured: 82 -> 77.6 ms per batch of 30 in pipeline.HostStream, tools/h2h_probe2.py)
-                st = dict(idx=list(range(len(imgs_ds)))[lo:hi], res=res, events=events, gts=gts, st_all=st_all,
-                          status_h=status_h, computed=computed, dev=(road_d, cl_d, conf_d), fig=fig)
-                t_enq = time.time()
-                if prev is not None:
-                    finalize(prev)
-                    if trace:
-                        print('trace batch %d: wait_load %.1f ms, enqueue %.1f ms, finalize(prev) %.1f ms, device gap '
-                              'done(prev)->start %.1f ms, device batch(prev) %.1f ms'
-                              % (bi, (t_loaded - st_all) * 1e3, (t_enq - t_loaded) * 1e3, (time.time() - t_enq) * 1e3,
-                                 prev['done'].elapsed_time(events['start']) if False else -1.0,
-                                 prev['events']['start'].elapsed_time(prev['computed'])), file=sys.stderr)
-                prev = st
-            if prev is not None:
-                finalize(prev)
+            _AsyncLoop(pipe, writer, figures).run(loader, len(imgs_ds))
         else:
-            for bi, (lo, hi) in enumerate(ranges):
-                st_all = time.time()
-                imgs, ready, _gts, _gt_dev, _u8 = queue.pop(0).result()
-                if ready is not None:
-                    torch.cuda.current_stream().wait_event(ready)
-                    if isinstance(imgs, torch.Tensor):
-                        imgs.record_stream(torch.cuda.current_stream())
-                if bi + depth < len(ranges):
-                    queue.append(loader.submit(load, ranges[bi + depth][0], ranges[bi + depth][1]))
-                res = pipe.run(imgs, orig_ds.batch(lo, hi, workers)) if originals else pipe.run(imgs)
-                times = pipe.elapsed_times()
-                cluster, road = res.masks_to_host()
-                info = res.info.cpu().numpy()
-                n_sp = res.n_labels.cpu().numpy()
-                # a re-labelled image (last batch shifted back, :539-542) must overwrite its earlier files:
-                # wait for the previous batch's writers before queueing this batch's
-                # (`pending` keeps them until they are drained, so that the finally clause still sees the
-                # successful ones if one of them failed)
-                drain_all()
-                for j, i in enumerate(list(range(len(imgs_ds)))[lo:hi]):
-                    pending.append(workers.submit(finish, i, road[j], cluster[j], int(n_sp[j]), info, times, st_all))
+            _simple_loop(pipe, loader, writer, len(imgs_ds), orig_ds)
     finally:
-        # whatever was computed before an error (corrupt PNG, device status, OOM) still reaches disk
-        ok = [f for f in pending if f.exception() is None]
-        bad = [f for f in pending if f.exception() is not None]
-        drain(ok)
-        workers.shutdown()
-        loader.shutdown()
-        if decoder is not None:
-            decoder.close()
-        # the figures' context goes now, not whenever a collection finds it (drn.py, _graph_capture: a context freed while
-        # a later call of this function captures its graph invalidates the capture)
-        fig_eng = figures.pop('eng', None)
-        figures.clear()
-        if fig_eng is not None:
-            fig_eng.close()
-    if bad:
-        raise bad[0].exception()
+        # after an error: the successful images reach disk, the pools, the decoder and the figures' context go, and only
+        # then is the first failed image's error raised
+        failed = writer.close()
+        if loader is not None:
+            loader.close()
+        if figures is not None:
+            figures.close()
+    if failed is not None:
+        raise failed
     if ws > 1:
-        # one collective: fixed-size records (scores + the stage timers of the image's batch); rank 0
-        # rebuilds the lines it did not produce from them (file names come from the shared lists)
-        allrec = spdist.gather_records(np.array(records, np.int64).reshape(-1, spdist.RECORD_WIDTH))
-        if rank == 0:
-            order = np.argsort(allrec[:, 0], kind='stable') if len(allrec) else []
-            for r in allrec[order]:                                     # index order
-                i = int(r[0])
-                if i in own:
-                    line = own[i]
-                else:
-                    TP, FP, FN, TN = int(r[4]), int(r[2]), int(r[3]), int(r[1])
-                    conf = np.array([[TN, FP], [FN, TP]], np.float64)
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        iou = np.diag(conf) / (conf.sum(1) + conf.sum(0) - np.diag(conf))
-                    sc = dict(road_iou=float(iou[1]), non_road_iou=float(iou[0]),
-                              precision=float(TP / (TP + FP)) if TP + FP else None,
-                              recall=float(TP / (TP + FN)) if TP + FN else None, TP=TP, FP=FP, FN=FN)
-                    timers = spdist.unpack_timers(r)
-                    line = result_line(args, imgs_ds._paths[i], labels_ds._paths[i], sc, {}, time.time())
-                    line['gpu'] = int(timers.pop('gpu', args.gpu))
-                    line.update(timers)                                  # time_* and elapsed_time of its rank
-                append_result_line(path, line)
-        spdist.barrier()
+        _write_gathered_lines(args, imgs_ds, labels_ds, writer, rank)
     if getattr(args, 'label_zip', None) and rank == 0:
         print('label archive: %d masks -> %s' % (write_label_zip(args.out_dir, args.label_zip), args.label_zip))
     return 0
@@ -885,7 +955,6 @@ def main_labelfree(argv=None):
     os.makedirs(args.out_dir, exist_ok=True)
     start, end = _effective_range(args, len(ds))
     from PIL import Image
-    from concurrent.futures import ThreadPoolExecutor
     io_pool = ThreadPoolExecutor(max_workers=max(1, args.io_threads))
     if args.png_encoder == 'device':
         try:
@@ -897,7 +966,7 @@ def main_labelfree(argv=None):
         batch = ds.batch(lo, hi, io_pool) if args.host_resize else ds.batch_device(lo, hi, io_pool, ops.engine())   # same thread
         res = pipe.run(batch)
         _, road = res.masks_to_host()
-        for j, i in enumerate(list(range(len(ds)))[lo:hi]):
+        for j, i in enumerate(_indices(len(ds), lo, hi)):
             rm = road[j]
             if rm.shape != tuple(args.label_shape):                    # :62-67
                 rm = resize_nearest(rm, tuple(args.label_shape))
@@ -928,11 +997,7 @@ def _labelfree_device_png(args, pipe, ds, img_fns, io_pool, start, end):
     def finalize(st):
         res, slot = st['res'], st['slot']
         st['encoded'].synchronize()         # the batch's one wait: mask, payload, lengths and status are there
-        eng.raise_on_word(st['status_h'])
-        if st['fail_h'] is not None:
-            res.check_retry(st['fail_h'])
-        elif getattr(res, 'retry_info', None) is not None:
-            res.check_retry()
+        _settle(eng, res, st['status_h'], st['fail_h'])
         # a re-labelled image (the last batch shifted back) must overwrite its earlier file, and the buffer set that
         # the batch before last used is free once its writers are through
         drain()
@@ -956,7 +1021,7 @@ def _labelfree_device_png(args, pipe, ds, img_fns, io_pool, start, end):
                 encoded = torch.cuda.Event()
                 encoded.record(res.stream)
             st = dict(res=res, slot=slot, fns=[os.path.join(args.out_dir, os.path.basename(img_fns[i]))
-                                               for i in list(range(len(ds)))[lo:hi]],
+                                               for i in _indices(len(ds), lo, hi)],
                       status_h=status_h, fail_h=fail_h, encoded=encoded)
             if prev is not None:
                 finalize(prev)
